@@ -6,14 +6,17 @@ contiguous point range (inputs already resident in its HBM), the per-rank partia
 (96 bytes each) are exchanged with one RCCL all-gather, and every rank folds them in rank order.
 Total work is fixed as the GPU count grows => "scaling": "strong".  value = ms per step, max over ranks.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
         python bench.py --gpus N --in-process      (one process, msm_multi: a context + host thread per device, in-library RCCL)
         ... --log-n 24            BASELINE config 4 (2^21 points per GPU on 8 GPUs)
         ... --log-n 26 --streamed BASELINE config 5 (host->HBM chunks overlapped with the accumulation; 2^23 points per GPU on 8)
-Prints ONE JSON line on rank 0 and exits non-zero if the result of the last timed step is not bit-exact.  The oracle
-(oracle/) is used only for the cpu_baseline leg and as a checker outside the timed region; inputs come from the hooks build
-(libmsm_hip_hooks.so: generator, calibration), the timed path is the product library (libmsm_hip.so).
+A plain run sets up, warms up, times --steps steps, writes the last step's result if --dump-outputs is given and prints ONE
+JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds everything else after the
+timed steps: the closed-form correctness gate (exit non-zero if any timed step is not bit-exact), clocks, rooflines, the stage
+breakdown, the exchange figures, the host-pointer legs and the CPU baseline.  The oracle (oracle/) is used only by --full, for
+the cpu_baseline leg and as a checker outside the timed region; inputs come from the hooks build (libmsm_hip_hooks.so:
+generator, calibration), the timed path is the product library (libmsm_hip.so).
 """
 import argparse
 import json
@@ -66,7 +69,7 @@ def kernel_source_hash():
     return h.hexdigest()[:16]
 
 
-EXTRAS_DEADLINE_S = int(os.environ.get("MSM_BENCH_EXTRAS_DEADLINE_S", "420"))  # the untimed legs of a default run take ~6 s
+EXTRAS_DEADLINE_S = int(os.environ.get("MSM_BENCH_EXTRAS_DEADLINE_S", "420"))  # the untimed legs of a --full run take ~6 s
 
 # one mixed addition (ec_bn254.hpp xyzz_madd, the loop body of k_accumulate_pieces): 6 fp_mul + 2 fp_sqr + 1 fused fp_mul_add
 MADS_PER_ADD = 6 * 162 + 2 * 126 + 243           # v_mad_u64_u32 instructions
@@ -139,6 +142,17 @@ def timed_calls(fn, reps, warm=1, warm_s=0.1):
     return r, ts[len(ts) // 2], ts[0]
 
 
+def dump_outputs(d, res):
+    """--dump-outputs: the group element the last timed step returned, as its caller reads it (MsmResult.affine_std: x then y in
+    standard form, 8 little-endian u32 words each, and is_infinity).  The words are written as their 64 bytes, so that a comparison
+    with a float tolerance still sees every bit.  The Jacobian words are not written: which representative of the point a step
+    returns depends on the order of a bucket's additions, which the sort does not fix; the point itself is fixed."""
+    os.makedirs(d, exist_ok=True)
+    xy = np.ascontiguousarray(res.affine_std, dtype="<u4").view(np.uint8).reshape(2, 32)
+    np.save(os.path.join(d, "affine_xy_bytes.npy"), xy.astype(np.float32))
+    np.save(os.path.join(d, "is_infinity.npy"), np.array([1.0 if res.is_infinity else 0.0], np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -166,7 +180,14 @@ def main():
     ap.add_argument("--debug-same-device", action="store_true",
                     help="functional check of the N>1 path on a 1-GPU box: every rank uses cuda:0 and the exchange runs over gloo / the host fold")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launched torchrun (0 = a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result to DIR/*.npy (float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check every step against the closed form and measure everything beyond the "
+                         "headline (clocks, rooflines, stage breakdown, exchange, host-pointer legs, CPU baseline)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` started plainly (no torchrun around it): start the N ranks ourselves -- as a CHILD process, before
     # anything here has touched the GPU (never a re-exec) -- relay rank 0's JSON line and exit with the child's code.
@@ -311,6 +332,29 @@ def main():
             exch_ms_sum += md.last_exchange_ms(xdev)
     fence()
     elapsed = time.perf_counter() - t0
+    if world > 1:  # value = the slowest rank's time
+        t = torch.tensor([elapsed], dtype=torch.float64, device=xdev if xdev is not None else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_per_step = elapsed * 1e3 / args.steps
+    headline = {"metric": "BN254 G1 MSM latency (ms) at N=2^%d, bit-exact vs arkworks-equivalent oracle" % args.log_n,
+                "value": round(ms_per_step, 4), "unit": "ms", "n_gpus": nshards, "steps": args.steps, "warmup": args.warmup,
+                "pre_warm_steps": pre_warm_steps, "ms_per_step": round(ms_per_step, 4), "higher_is_better": False, "scaling": "strong",
+                "vs_baseline": None, "dtype": "u32", "data": "synthetic"}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline))
+            sys.stdout.flush()
+        if ctx is not None:
+            ctx.close()
+        if multi is not None:
+            multi.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     clk_loop = clk_single = None
     if ctx is not None:
         clk_loop = ctx.clock_stats()  # k_accumulate_pieces' own cycle / constant-rate counters over the timed launches
@@ -356,9 +400,6 @@ def main():
     # really saw, what the exchange cost, and every rank's own shard time
     exchange = None
     if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=xdev if xdev is not None else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
         per_rank = [None] * world
         dist.all_gather_object(per_rank, {"rank": rank, "device": torch.cuda.current_device(), "shard_points": n_local,
                                           "shard_ms": shard_ms_acc[0] / max(1, shard_ms_acc[1]), "exchange_ms": exch_ms_sum / max(1, args.steps),
@@ -388,7 +429,6 @@ def main():
                                  for g in range(multi.num_devices)],
                     "note": "last step; shard ms = wall clock of each rank's local MSM on its host thread; sclk_ghz = the shader clock that rank's "
                             "k_accumulate_pieces measured for itself since the handle was created"}
-    ms_per_step = elapsed * 1e3 / args.steps
 
     # ---- correctness gate (outside the timed region): closed form (sum s_i k_i mod r) * G ----------
     dot = 0
@@ -469,11 +509,9 @@ def main():
                                     "detail": "offline rocprofv3 --pmc passes (tools/pmc_accumulate.sh + tools/pmc_sort_summarize.py); not measured in this run"}
                 break
         out = {
-            "metric": "BN254 G1 MSM latency (ms) at N=2^%d, bit-exact vs arkworks-equivalent oracle" % args.log_n,
-            "value": round(ms_per_step, 4), "unit": "ms", "n_gpus": nshards, "steps": args.steps, "warmup": args.warmup, "pre_warm_steps": pre_warm_steps,
+            **headline,
             "step_after_0.2s_idle_ms": round(after_idle_ms, 4) if after_idle_ms is not None else None,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": False, "scaling": "strong", "vs_baseline": None,
-            "dtype": "u32", "data": "synthetic", "source_hash": src_hash,
+            "source_hash": src_hash,
             "config": {"workload": "BN254 G1 variable-base MSM, N=2^%d, dynamic window + signed-digit buckets "
                                    "(BASELINE.json configs[%d]); bases k_i*G and scalars %s, "
                                    "point-range shards + all-gather of 96-byte partials"

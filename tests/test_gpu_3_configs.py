@@ -671,13 +671,35 @@ def test_bench_gpus_2_starts_without_torchrun():
     ranks itself (a child `python -m torch.distributed.run ...`, never a re-exec), relay rank 0's JSON line and exit code.  On this
     1-GPU box both ranks share cuda:0 (--debug-same-device: exchange over gloo)."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--debug-same-device", "--steps", "2", "--warmup", "1",
-                        "--log-n", "18", "--pre-warm-ms", "20", "--no-host-legs", "--no-cpu-baseline"],
+                        "--log-n", "18", "--pre-warm-ms", "20", "--no-host-legs", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["bit_exact"] and j["exchange"]["world_seen"] == 2 and j["config"]["n_per_gpu"] == 1 << 17
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_result(tmp_path):
+    """a plain `bench.py` run (no --full) times exactly --steps steps and prints the headline fields only; --dump-outputs writes the
+    point the last timed step returned, which must be the closed form of the benchmark's own seeded instance"""
+    d = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log-n", "14", "--pre-warm-ms", "20",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["value"] == j["ms_per_step"] > 0 and j["unit"] == "ms" and j["higher_is_better"] is False and j["dtype"] == "u32"
+    assert not {"bit_exact", "roofline", "cpu_baseline", "host_pointer_legs", "stage_ms_untimed_diagnostic_step"} & set(j)
+    n = 1 << 14
+    k = _ints(th.generate_scalars_host(0xB2540001, n, nonzero=True))  # bench.py BASE_SEED / SCALAR_SEED
+    s = _ints(th.generate_scalars_host(0xB2540002, n))
+    exp, exp_inf = _expected(sum(a * b for a, b in zip(k, s)))
+    xy = np.load(d / "affine_xy_bytes.npy")
+    assert xy.dtype == np.float32 and xy.shape == (2, 32)
+    assert (xy.astype(np.uint8).reshape(-1).view("<u4") == exp).all()
+    assert np.load(d / "is_infinity.npy").tolist() == [1.0 if exp_inf else 0.0]
 
 
 def test_two_ranks_bad_scalar_on_one_rank_fails_everywhere():

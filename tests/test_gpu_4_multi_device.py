@@ -226,7 +226,7 @@ def test_one_process_per_gpu_failing_rank_over_rccl():
 def test_bench_gpus_n_starts_plainly():
     """`python bench.py --gpus N` with NO torchrun around it (how the driver starts the N = 1 line) must launch its ranks itself"""
     G = _ndev()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(G), "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(G), "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -23,7 +23,7 @@ for rnd in range(rounds):
                 env[k_] = v_
             elif part != "base":
                 env["MSM_HIP_LIB"] = os.path.join(ROOT, "tools", "_ab", "libmsm_hip_%s.so" % part)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-host-legs"] + extra,
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-host-legs"] + extra,
                            capture_output=True, text=True, env=env)
         try:
             j = json.loads(p.stdout.strip().splitlines()[-1])

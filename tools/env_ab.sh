@@ -6,7 +6,7 @@ KV="$1"; shift
 line() { python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', 'logN', '$2', 'ms', d['value'], 'sort', d['stage_ms_untimed_diagnostic_step'].get('sort_ms'), 'reduce', d['stage_ms_untimed_diagnostic_step'].get('reduce_ms'), 'exact', d['bit_exact'])"; }
 for rnd in 1 2 3; do
   for n in ${*:-17 20}; do
-    python3 bench.py --log-n $n --no-cpu-baseline --no-host-legs 2>/dev/null | line "default      " $n
-    env "$KV" python3 bench.py --log-n $n --no-cpu-baseline --no-host-legs 2>/dev/null | line "$KV" $n
+    python3 bench.py --full --log-n $n --no-cpu-baseline --no-host-legs 2>/dev/null | line "default      " $n
+    env "$KV" python3 bench.py --full --log-n $n --no-cpu-baseline --no-host-legs 2>/dev/null | line "$KV" $n
   done
 done

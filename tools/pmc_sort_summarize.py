@@ -29,7 +29,7 @@ for k in SORT + OTHER:
 res = {"kernels": rows, "stream_fetch_correction": round(stream_factor, 3),
        "sort_hbm_bytes": sum(rows[k]["fetch_bytes"] + rows[k]["write_bytes"] for k in SORT if k in rows),
        "build": sys.argv[2] if len(sys.argv) > 2 else "?",
-       "how": "tools/pmc_accumulate.sh passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, --kernel-trace only, python3 bench.py --steps 3 --warmup 1 directly after `--`), "
+       "how": "tools/pmc_accumulate.sh passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, --kernel-trace only, python3 bench.py --full --steps 3 --warmup 1 directly after `--`), "
               "newest counter file of each pass; per-dispatch averages; fetches x the 16-B-per-lane stream factor of tools/calib_gather"}
 try:
     line = [l for l in open(f"{d}/bench_FETCH_SIZE.log") if l.startswith("{")][-1]

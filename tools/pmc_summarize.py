@@ -38,7 +38,7 @@ except Exception as e:
     res["n_local"], res["window_bits"] = None, None
 res["build"] = sys.argv[2] if len(sys.argv) > 2 else "?"
 res["how"] = ("tools/pmc_accumulate.sh on an MI355X gpurun box: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes "
-              "(with --kernel-trace only) around `python3 bench.py --steps 3 --warmup 1`; counters corrected with the factors measured "
+              "(with --kernel-trace only) around `python3 bench.py --full --steps 3 --warmup 1`; counters corrected with the factors measured "
               "by tools/calib_gather on the same box (64-B record gathers count exactly, 16 B/lane streams count 1/2, 144-B record "
               "stores over-count by ~5.6 %)")
 json.dump(res, open(f"{d}/summary.json", "w"), indent=1)

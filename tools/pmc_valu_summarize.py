@@ -32,7 +32,7 @@ for k in ("k_accumulate_pieces", "k_pair_level8", "k_combine_pieces", "k_fine_so
     if "SQ_THREAD_CYCLES_VALU" in c and c.get("SQ_ACTIVE_INST_VALU"):
         e["valu_util_frac"] = round(c["SQ_THREAD_CYCLES_VALU"] / (c["SQ_ACTIVE_INST_VALU"] * 64), 4)
     out[k] = e
-res = {"kernels": out, "source": "tools/pmc_valu.sh: rocprofv3 --pmc (SQ_* / GRBM_GUI_ACTIVE), --kernel-trace only, python3 bench.py --steps 3 --warmup 1 directly after `--`; "
+res = {"kernels": out, "source": "tools/pmc_valu.sh: rocprofv3 --pmc (SQ_* / GRBM_GUI_ACTIVE), --kernel-trace only, python3 bench.py --full --steps 3 --warmup 1 directly after `--`; "
                                    "SQ_ACTIVE_INST_* and SQ_WAVE_CYCLES count quad-cycles (MI355X_MICROARCH.md)"}
 a = out.get("k_accumulate_pieces", {})
 for k in ("valu_busy_frac", "valu_util_frac"):

@@ -4,7 +4,7 @@ import json, subprocess, sys
 for n in [int(x) for x in (sys.argv[1:] or "21 22 23 24".split())]:
     row = []
     for c in (16, 17, 18):
-        p = subprocess.run([sys.executable, "bench.py", "--log-n", str(n), "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--window-bits", str(c)],
+        p = subprocess.run([sys.executable, "bench.py", "--full", "--log-n", str(n), "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--window-bits", str(c)],
                            capture_output=True, text=True)
         try:
             j = json.loads(p.stdout.strip().splitlines()[-1]); st = j["stage_ms_untimed_diagnostic_step"]

@@ -7,7 +7,7 @@ for n in sizes:
     for c in [int(x) for x in (os.environ.get("CS") or "0,7,8,9,10,11,12,13,14,15,16").split(",")]:
         if c and (1 << (c - 1)) > (1 << n) * 4:
             continue
-        p = subprocess.run([sys.executable, "bench.py", "--log-n", str(n), "--steps", "60", "--warmup", "5", "--no-cpu-baseline", "--no-host-legs",
+        p = subprocess.run([sys.executable, "bench.py", "--full", "--log-n", str(n), "--steps", "60", "--warmup", "5", "--no-cpu-baseline", "--no-host-legs",
                             "--window-bits", str(c)], capture_output=True, text=True)
         try:
             j = json.loads(p.stdout.strip().splitlines()[-1])

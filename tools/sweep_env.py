@@ -12,7 +12,7 @@ res = {v: [] for v in vals}
 for rnd in range(3):
     for v in vals:
         env = dict(os.environ, **{name: v})
-        p = subprocess.run([sys.executable, "bench.py", "--steps", "30", "--warmup", "3", "--no-cpu-baseline"] + extra, capture_output=True, text=True, env=env)
+        p = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "30", "--warmup", "3", "--no-cpu-baseline"] + extra, capture_output=True, text=True, env=env)
         j = json.loads(p.stdout.strip().splitlines()[-1])
         res[v].append((j["value"], j["stage_ms_untimed_diagnostic_step"]["reduce_ms"], j["bit_exact"]))
 for v in vals:
