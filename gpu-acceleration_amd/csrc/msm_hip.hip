@@ -38,9 +38,11 @@
 
 #include "../../include/msm_hip.h"
 #include "host_g1.hpp"
+#include "host_g2.hpp"
 #include "msm_host_pool.hpp"
 #include "msm_planner.hpp"
 #include "msm_kernels.hpp"
+#include "msm_kernels_g2.hpp"
 
 namespace {
 
@@ -199,6 +201,8 @@ struct msm_ctx {
     uint32_t* h_flags = nullptr;  // pinned: the 8 flag words, as pairs as well
     std::vector<uint32_t> qsums;  // the bit sums of the call being finished, 24 words each, taken out of the pairs once every tag is the call's (gather_results)
     uint32_t flagw[8] = {};       // ... and its flag words
+    uint32_t* h_qsums2 = nullptr;  // pinned, G2 calls (msm_g2.inc; allocated by the first one): 48 (word, sequence number) pairs per bit sum
+    std::vector<uint32_t> qsums2;  // ... the G2 bit sums of the call being finished, 48 words each
     // resident bases
     size_t resident_n = 0;
     bool resident_has_inf = false;
@@ -366,8 +370,9 @@ struct PipeState {
 // fixed once per instance, so that a smaller chunk can never need more pieces or partial-sum slots than the workspace sized for the first
 // one holds (lengths re-derived per chunk could outgrow the 12.5 % slack of ensure() and make it reallocate -- a device
 // synchronisation -- with chunks in flight).
+// rec_bytes: bytes per bucket record (XB: G1; a G2 call passes its own, msm_g2.inc)
 int32_t pipe_prepare(msm_ctx* c, size_t n_real, size_t plan_n, uint32_t extra_flags, hipStream_t st, PipeState* ps, uint32_t table_c = 0,
-                     uint32_t table_f = 1, const PipeState* first = nullptr) {
+                     uint32_t table_f = 1, const PipeState* first = nullptr, size_t rec_bytes = XB) {
     if (trace_enabled() && c->flags_clean) c->t_prepare = std::chrono::steady_clock::now();  // (flags_clean: first prepare of a call)
     if (n_real > 0x3FFFFFFFull) return fail(c, MSM_ERR_BAD_ARG, "n = %zu exceeds 2^30-1 points per context call", n_real);
     // (a table call re-derives the plan its upload made: same width, and the split wherever make_table_plan allowed it -- the caller
@@ -411,9 +416,9 @@ int32_t pipe_prepare(msm_ctx* c, size_t n_real, size_t plan_n, uint32_t extra_fl
     if ((rc = ensure(c, c->hist, tb * 4))) return rc;
     if ((rc = ensure(c, c->offsets, (tb + 1) * 4))) return rc;
     if ((rc = ensure(c, c->blocksums, ((size_t)ntiles + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->buckets, tb * XB))) return rc;
+    if ((rc = ensure(c, c->buckets, tb * rec_bytes))) return rc;
     if ((rc = ensure(c, c->sorttmp, pairs * 4))) return rc;  // stages the two-level sort
-    if ((rc = ensure(c, c->partials, maxpartials * XB))) return rc;
+    if ((rc = ensure(c, c->partials, maxpartials * rec_bytes))) return rc;
     if ((rc = ensure(c, c->plist, ps->maxpieces * 16))) return rc;
     if ((rc = ensure(c, c->pbase, tb * 4))) return rc;
     // (no memset: every sort chain zeroes the bins itself, at its head -- msmk::clear_piece_bins in k_decompose* / k_coarse_hist)
@@ -428,7 +433,7 @@ int32_t pipe_prepare(msm_ctx* c, size_t n_real, size_t plan_n, uint32_t extra_fl
     }
     // two lists: the two-piece buckets from entry 0 (at most tb of them), those of 3 .. LONG_SPAN-1 pieces from entry tb (piece_tally_publish)
     if ((rc = ensure(c, c->midlist, (tb + std::min(tb, maxpartials / 3) + 16) * 4))) return rc;
-    if ((rc = ensure(c, c->rc, (tb + tb / 2 + 4) * XB))) return rc;  // two families x (1/2 + 1/4) ping-pong levels
+    if ((rc = ensure(c, c->rc, (tb + tb / 2 + 4) * rec_bytes))) return rc;  // two families x (1/2 + 1/4) ping-pong levels
     if ((rc = ensure(c, c->flags, 64))) return rc;
     return MSM_OK;
 }
@@ -799,27 +804,38 @@ int32_t enqueue_reduce(msm_ctx* c, const PipeState& ps, hipStream_t st, uint32_t
 // add nothing because the shift of the top segment is serial.  TWO threads by default: every further worker lowers the median by a
 // few microseconds and raises the MEAN through 2-8 ms outliers in ~1.3 % of the calls (busy hosts; a pool of 15: 2.5 %) --
 // tools/step_jitter.py.  With one shared bucket array (full window table) the chain is cbits - 1 positions long instead of 254.
-hostg1::Jac host_finish(msm_ctx* c, const uint32_t* h_qsums, const PipeState& g) {
+// The group is a template argument (G1: HostG1 below, G2: HostG2 in msm_g2.inc): the bit sums are G::WORDS words each.
+struct HostG1 {
+    using Jac = hostg1::Jac;
+    static constexpr size_t WORDS = 24;
+    static Jac identity() { return hostg1::identity(); }
+    static Jac jdbl(const Jac& p) { return hostg1::jdbl(p); }
+    static Jac jadd(const Jac& p, const Jac& q) { return hostg1::jadd(p, q); }
+    static Jac load_jac(const uint32_t* w) { return hostg1::load_jac(w); }
+};
+template <class G>
+typename G::Jac host_finish_group(msm_ctx* c, const uint32_t* h_qsums, const PipeState& g) {
     Range r_("msm:host_finish");
+    using Jac = typename G::Jac;
     const uint32_t V = g.sW, kb = g.kb, rkb = g.rkb, PW = 1u << g.pw_bits, spacing = g.cbits * g.tf;
     const uint32_t npos = spacing * (V - 1) + (kb > 0 ? kb : 1);  // positions 0 .. npos-1 carry terms
-    auto qsum = [&](uint32_t v, uint32_t q, uint32_t u) { return hostg1::load_jac(h_qsums + ((size_t)(v * PW + q) * (rkb + 1) + u) * 24); };
+    auto qsum = [&](uint32_t v, uint32_t q, uint32_t u) { return G::load_jac(h_qsums + ((size_t)(v * PW + q) * (rkb + 1) + u) * G::WORDS); };
     auto segment = [&](uint32_t lo, uint32_t hi) {             // sum over p in [lo, hi) of 2^p * term(p)
-        hostg1::Jac acc = hostg1::identity();
+        Jac acc = G::identity();
         for (uint32_t p = hi; p-- > lo;) {
-            acc = hostg1::jdbl(acc);
+            acc = G::jdbl(acc);
             const uint32_t v = p / spacing, u = p % spacing;
             if (v == V - 1 && u >= g.top_bits) {
                 // index bits of a spread top window that hold point-index bits, not the digit (msmplan::glv_top_digit_bits): no weight
             } else if (u < rkb)
-                for (uint32_t q = 0; q < PW; q++) acc = hostg1::jadd(acc, qsum(v, q, u));
+                for (uint32_t q = 0; q < PW; q++) acc = G::jadd(acc, qsum(v, q, u));
             else if (u < kb)
                 for (uint32_t q = 0; q < PW; q++)
-                    if ((q >> (u - rkb)) & 1u) acc = hostg1::jadd(acc, qsum(v, q, rkb));
+                    if ((q >> (u - rkb)) & 1u) acc = G::jadd(acc, qsum(v, q, rkb));
             if (u == 0)
-                for (uint32_t q = 0; q < PW; q++) acc = hostg1::jadd(acc, qsum(v, q, rkb));
+                for (uint32_t q = 0; q < PW; q++) acc = G::jadd(acc, qsum(v, q, rkb));
         }
-        for (uint32_t k = 0; k < lo; k++) acc = hostg1::jdbl(acc);
+        for (uint32_t k = 0; k < lo; k++) acc = G::jdbl(acc);
         return acc;
     };
     const int nseg = c->pool ? std::min<int>(c->pool->size() + 1, 8) : 1;
@@ -835,12 +851,13 @@ hostg1::Jac host_finish(msm_ctx* c, const uint32_t* h_qsums, const PipeState& g)
         run += wgt;
         bound[k + 1] = k + 1 == nseg ? npos : (uint32_t)(npos * (run / tot) + 0.5);
     }
-    std::vector<hostg1::Jac> part((size_t)nseg);
+    std::vector<Jac> part((size_t)nseg);
     c->pool->run(nseg, [&](int k) { part[(size_t)k] = segment(bound[k], bound[k + 1]); });  // job 0 (the longest) is taken first
-    hostg1::Jac total = part[0];
-    for (int k = 1; k < nseg; k++) total = hostg1::jadd(total, part[(size_t)k]);
+    Jac total = part[0];
+    for (int k = 1; k < nseg; k++) total = G::jadd(total, part[(size_t)k]);
     return total;
 }
+hostg1::Jac host_finish(msm_ctx* c, const uint32_t* h_qsums, const PipeState& g) { return host_finish_group<HostG1>(c, h_qsums, g); }
 
 constexpr int32_t ARK_RETRY_SLOW = 1;  // (internal, never handed out: see KIND_ARKFAST)
 int32_t check_flags(msm_ctx* c, const uint32_t* h_flags) {
@@ -1556,6 +1573,7 @@ void msm_ctx_destroy(msm_ctx* c) {
                           &c->rbases,  &c->rinf,      &c->clk,     &c->phist,   &c->pcursor, &c->pbase,  &c->plist,  &c->partials};
         for (DevBuf* b : bufs) release(*b);
         if (c->h_qsums) (void)hipHostFree(c->h_qsums);
+        if (c->h_qsums2) (void)hipHostFree(c->h_qsums2);
         if (c->h_flags) (void)hipHostFree(c->h_flags);
         release(c->sibases);
         for (int i = 0; i < STREAM_SLOTS; i++) {
@@ -2061,6 +2079,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 }  // extern "C"
 
 #include "msm_multi.inc"
+#include "msm_g2.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS
 #include "msm_testhooks.inc"

@@ -1,0 +1,278 @@
+// msm_kernels_g2.hpp -- the gfx950 kernels of the BN254 G2 MSM: only the point side.  The scalar side -- decomposition (GLV split included), the
+// counting sort, the piece plan (plist, pbase, the mid / long lists) -- is the G1 pipeline's, unchanged (msm_kernels.hpp): it never looks at a point.
+//
+// Data layout in HBM (little-endian u32 words):
+//   g2 bases   n x 32 (2n x 32 with the GLV split: phi(P_i) at index n + i)   x.c0 x.c1 y.c0 y.c1, each 8 packed words, INTERNAL domain, canonical
+//   buckets    tb x 72     XYZZ over Fq2: X.c0 X.c1 Y.c0 Y.c1 ZZ.c0 ZZ.c1 ZZZ.c0 ZZZ.c1, 9 limbs each (288 B)
+//   partials   x 72        the pieces' sums of split buckets, as k_accumulate_pieces writes them (same piece format, same slots)
+// Every addition is one lane's (no eight-lane variants): a G2 addition is ~3x a G1 one, so the lone dependent chains of the reduction weigh less
+// against the work, and one call site per kernel keeps the code (each inlined complete addition is ~100 KB) out of the instruction cache's way.
+#pragma once
+#include "msm_kernels.hpp"
+#include "ec_g2_bn254.hpp"
+
+namespace msmk {
+
+constexpr int XW2 = 72;   // words per G2 XYZZ record in HBM / LDS
+constexpr int BW2 = 32;   // words per G2 base record
+// beta^2 = -beta - 1 (mod p), standard form: phi2(x, y) = (beta^2 x, y) = lambda * (x, y) on G2, lambda the scalar of the G1 split (glv_bn254.hpp)
+constexpr uint32_t BETA2_STD[8] = {0x77fffffeu, 0x57634731u, 0xacdb5c4fu, 0xd4f263f1u, 0xa0d48bacu, 0x59e26bceu, 0x00000000u, 0x00000000u};
+
+__device__ __forceinline__ fp2 load_fp2_packed(const uint32_t* p) { return fp2{load_fp_packed(p), load_fp_packed(p + 8)}; }
+__device__ __forceinline__ void load_fp9(fp& r, const uint32_t* p) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.v[i] = p[i];
+}
+__device__ __forceinline__ void store_fp9(uint32_t* p, const fp& v) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) p[i] = v.v[i];
+}
+__device__ __forceinline__ xyzz2 load_xyzz2(const uint32_t* p) {
+    xyzz2 r;
+    load_fp9(r.x.c0, p), load_fp9(r.x.c1, p + 9), load_fp9(r.y.c0, p + 18), load_fp9(r.y.c1, p + 27);
+    load_fp9(r.zz.c0, p + 36), load_fp9(r.zz.c1, p + 45), load_fp9(r.zzz.c0, p + 54), load_fp9(r.zzz.c1, p + 63);
+    return r;
+}
+__device__ __forceinline__ void store_xyzz2(uint32_t* p, const xyzz2& v) {
+    store_fp9(p, v.x.c0), store_fp9(p + 9, v.x.c1), store_fp9(p + 18, v.y.c0), store_fp9(p + 27, v.y.c1);
+    store_fp9(p + 36, v.zz.c0), store_fp9(p + 45, v.zz.c1), store_fp9(p + 54, v.zzz.c0), store_fp9(p + 63, v.zzz.c1);
+}
+
+// Caller words -> internal records: one thread per Fq component (4 per point).  glv: the record of phi2(P_i) at index n + i -- both x components
+// times beta^2, y as it is (the k_convert_bases convention).
+__global__ void __launch_bounds__(256) k_g2_convert(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n, uint32_t mont_form,
+                                                    uint32_t glv) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 4u * n) return;
+    const uint32_t pt = i >> 2, which = i & 3u;
+    fp v = fp_mul(load_fp_packed(in + (size_t)i * 8), mont_form ? fp_const(FP29_IN_MONT) : fp_const(FP29_IN_STD));  // < 1.01p
+    uint32_t w[8];
+    fp_pack(w, fp_reduce_lt2p(v));
+    store_words8(out + ((size_t)pt * 4 + which) * 8, w);
+    if (glv) {
+        if (which < 2) fp_pack(w, fp_reduce_lt2p(fp_mul(v, fp_from_std(BETA2_STD))));
+        store_words8(out + ((size_t)(n + pt) * 4 + which) * 8, w);
+    }
+}
+
+// Buckets that no entry falls into: the identity (an all-zero record).  The G1 piece tally writes ITS identity record there; a G2 call runs the
+// tally in its "into" form, which leaves the bucket array alone, and clears the empty buckets here instead.
+__global__ void __launch_bounds__(256) k_g2_clear_empty(const uint32_t* __restrict__ offsets, uint32_t total_buckets, uint32_t* __restrict__ buckets) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // 8 lanes per bucket, 9 words each
+    const uint32_t k = t >> 3, part = t & 7u;
+    if (k >= total_buckets || offsets[k + 1] != offsets[k]) return;
+    uint32_t* p = buckets + (size_t)k * XW2 + part * 9;
+#pragma unroll
+    for (int i = 0; i < 9; i++) p[i] = 0;
+}
+
+// One thread per piece of plist (k_piece_scatter's list, longest first): the entries sorted[j0 .. j0 + len) folded by mixed additions; the sum goes
+// to the bucket (PF_WHOLE) or to partials[pc.w].  The next entry's 128-byte record is in flight while the current one is added.
+// Clock probe of the launch's first workgroup into clk, as k_accumulate_pieces does (msm_get_clock_stats).
+__global__ void __launch_bounds__(256) k_g2_accumulate(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
+                                                       const uint4* __restrict__ plist, const uint32_t* __restrict__ npieces_ptr,
+                                                       uint32_t* __restrict__ buckets, uint32_t* __restrict__ partials,
+                                                       unsigned long long* __restrict__ clk) {
+    const bool probe = blockIdx.x == 0;
+    long long clk_c0 = 0, clk_w0 = 0;
+    if (probe) clk_c0 = clock64(), clk_w0 = wall_clock64();
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= *npieces_ptr) return;
+    const uint4 pc = plist[t];
+    const uint32_t k = pc.x, j0 = pc.y, len = pc.z & PF_LEN_MASK, j1 = j0 + len;
+    auto record = [&](uint32_t e) { return reinterpret_cast<const uint4*>(bases + (size_t)(e & ~SIGN_BIT) * BW2); };
+    xyzz2 acc = xyzz2_identity();
+    uint32_t e_cur = sorted[j0];
+    uint4 g[8];
+    {
+        const uint4* bp = record(e_cur);
+#pragma unroll
+        for (int i = 0; i < 8; i++) g[i] = bp[i];
+    }
+    for (uint32_t j = j0; j < j1; j++) {
+        affine2 q;
+        {
+            uint32_t w[4][8];
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const uint4 a = g[2 * c], b = g[2 * c + 1];
+                w[c][0] = a.x, w[c][1] = a.y, w[c][2] = a.z, w[c][3] = a.w, w[c][4] = b.x, w[c][5] = b.y, w[c][6] = b.z, w[c][7] = b.w;
+            }
+            q.x = fp2{fp_unpack(w[0]), fp_unpack(w[1])};
+            q.y = fp2{fp_unpack(w[2]), fp_unpack(w[3])};
+        }
+        if (e_cur & SIGN_BIT) q.y = fp2_neg<2>(q.y);  // canonical y < p  ->  2p - y < 2
+        const uint32_t e_nxt = sorted[min(j + 1, j1 - 1)];
+        {
+            const uint4* bp = record(e_nxt);
+#pragma unroll
+            for (int i = 0; i < 8; i++) g[i] = bp[i];
+        }
+        xyzz2_madd(acc, q);
+        e_cur = e_nxt;
+    }
+    store_xyzz2((pc.z & PF_WHOLE) ? buckets + (size_t)k * XW2 : partials + (size_t)pc.w * XW2, acc);
+    if (probe && threadIdx.x == 0) {  // [0] shader cycles, [1] constant-rate ticks, [2] samples, [3] mixed additions of the sampled thread
+        atomicAdd(clk + 0, (unsigned long long)(clock64() - clk_c0));
+        atomicAdd(clk + 1, (unsigned long long)(wall_clock64() - clk_w0));
+        atomicAdd(clk + 2, 1ull);
+        atomicAdd(clk + 3, (unsigned long long)len);
+    }
+}
+
+// Split buckets: the partial sums partials[pbase[k] .. + m) folded into buckets[k], from the lists the piece kernels built.
+//   workgroups [0, G2_LONG_BLOCKS): long list, one workgroup per (bucket, segment of LONG_SEG pieces): each of G2_TREE lanes folds its share of the
+//       segment serially, an LDS tree of one-lane additions folds the G2_TREE sums; a bucket of several segments parks every segment's sum in the
+//       segment's first slot and the LAST workgroup to arrive (counter long_done[first item of the bucket], reset for the next call) folds them.
+//   the rest: one LANE per bucket of 2 .. LONG_SPAN-1 pieces (the two-piece list, then the 3..7-piece list at mid_list[mid3_off ..)).
+constexpr uint32_t G2_TREE = 128;          // records of a long item's LDS tree (36 KB)
+constexpr uint32_t G2_COMBINE_BLOCK = 256;
+constexpr uint32_t G2_LONG_BLOCKS = 1024, G2_MID_BLOCKS = 256;
+__device__ __forceinline__ void g2_fold_segment(uint32_t* e, const uint32_t* partials, uint32_t base, uint32_t first, uint32_t stride, uint32_t count) {
+    __syncthreads();  // e is reused
+    const uint32_t t = threadIdx.x;
+    if (t < G2_TREE) {
+        xyzz2 acc = xyzz2_identity();
+#pragma unroll 1
+        for (uint32_t i = t; i < count; i += G2_TREE) acc = xyzz2_add(acc, load_xyzz2(partials + (size_t)(base + first + i * stride) * XW2));
+        store_xyzz2(e + (size_t)t * XW2, acc);
+    }
+#pragma unroll 1
+    for (uint32_t h = G2_TREE / 2; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) store_xyzz2(e + (size_t)t * XW2, xyzz2_add(load_xyzz2(e + (size_t)t * XW2), load_xyzz2(e + (size_t)(t + h) * XW2)));
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void g2_copy_record(uint32_t* dst, const uint32_t* src) {  // whole workgroup
+    for (uint32_t i = threadIdx.x; i < (uint32_t)XW2; i += blockDim.x) dst[i] = src[i];
+}
+__global__ void __launch_bounds__(G2_COMBINE_BLOCK) k_g2_combine(const uint32_t* __restrict__ offsets, uint32_t* __restrict__ partials,
+                                                                 uint32_t* __restrict__ buckets, uint32_t pmax, uint32_t psplit,
+                                                                 const uint32_t* __restrict__ pbase, const uint32_t* __restrict__ mid_count,
+                                                                 const uint32_t* __restrict__ mid2_count, const uint32_t* __restrict__ mid_list,
+                                                                 uint32_t mid3_off, const uint32_t* __restrict__ long_count,
+                                                                 const uint32_t* __restrict__ long_list, uint32_t* __restrict__ long_done,
+                                                                 const uint32_t* __restrict__ entries) {
+    __shared__ uint32_t e[G2_TREE * XW2];
+    __shared__ uint32_t s_last;
+    decode_piece_lengths(pmax, psplit, entries[0], entries[FLAG_NONEMPTY - FLAG_PAIRS]);  // (entries = flags + FLAG_PAIRS, as for k_combine_pieces)
+    if (blockIdx.x >= G2_LONG_BLOCKS) {
+        const uint32_t n2 = *mid2_count, n3 = *mid_count;
+        for (uint32_t i = (blockIdx.x - G2_LONG_BLOCKS) * blockDim.x + threadIdx.x; i < n2 + n3; i += G2_MID_BLOCKS * blockDim.x) {
+            const uint32_t k = i < n2 ? mid_list[i] : mid_list[mid3_off + (i - n2)];
+            uint32_t q;
+            const uint32_t m = piece_split(offsets[k + 1] - offsets[k], pmax, psplit, &q);
+            const uint32_t* p0 = partials + (size_t)pbase[k] * XW2;
+            xyzz2 acc = load_xyzz2(p0);
+#pragma unroll 1
+            for (uint32_t p = 1; p < m; p++) acc = xyzz2_add(acc, load_xyzz2(p0 + (size_t)p * XW2));
+            store_xyzz2(buckets + (size_t)k * XW2, acc);
+        }
+        return;
+    }
+    const uint32_t nlong = *long_count;
+    for (uint32_t item = blockIdx.x; item < nlong; item += G2_LONG_BLOCKS) {  // (uniform per workgroup)
+        const uint32_t k = long_list[2 * (size_t)item], seg = long_list[2 * (size_t)item + 1];
+        uint32_t q;
+        const uint32_t cnt = piece_split(offsets[k + 1] - offsets[k], pmax, psplit, &q), nseg = (cnt + LONG_SEG - 1) / LONG_SEG, base = pbase[k];
+        const uint32_t first = seg * LONG_SEG, count = min(LONG_SEG, cnt - first);
+        g2_fold_segment(e, partials, base, first, 1, count);
+        if (nseg == 1) {
+            g2_copy_record(buckets + (size_t)k * XW2, e);
+            continue;
+        }
+        g2_copy_record(partials + (size_t)(base + first) * XW2, e);  // park the segment's sum in its first slot (only this workgroup read it)
+        __threadfence();
+        __syncthreads();
+        if (threadIdx.x == 0) s_last = atomicAdd(&long_done[item - seg], 1u) == nseg - 1 ? 1u : 0u;
+        __syncthreads();
+        if (!s_last) continue;  // uniform
+        __threadfence();        // see the other segments' sums
+        g2_fold_segment(e, partials, base, 0, LONG_SEG, nseg);
+        g2_copy_record(buckets + (size_t)k * XW2, e);
+        if (threadIdx.x == 0) long_done[item - seg] = 0;  // ready for the next call
+    }
+}
+
+// One pairwise level of both families (k_pair_level's job layout), one lane per addition.
+__global__ void __launch_bounds__(256) k_g2_pair_level(pair_job ja, pair_job jb) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    pair_job j = ja;
+    if (t >= ja.n_out) {
+        t -= ja.n_out;
+        j = jb;
+        if (t >= jb.n_out) return;
+    }
+    const size_t i0 = (size_t)2 * (t / j.B) * j.B + (t % j.B);
+    store_xyzz2(j.out + (size_t)t * XW2, xyzz2_add(load_xyzz2(j.in + i0 * XW2), load_xyzz2(j.in + (i0 + j.B) * XW2)));
+}
+
+__device__ __forceinline__ fp shfl_down_fp9(const fp& a, int d) {
+    fp r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.v[i] = __shfl_down(a.v[i], d, 64);
+    return r;
+}
+__device__ __forceinline__ fp2 shfl_down_fp2(const fp2& a, int d) { return fp2{shfl_down_fp9(a.c0, d), shfl_down_fp9(a.c1, d)}; }
+
+// The bit sums: one wavefront per (window, bit) over R[w][0..n_hi) / C[w][0..n_lo) (k_reduce_bits' selection), published as XYZZ -> Jacobian ->
+// R = 2^256 Montgomery words, 48 per sum, each as a (word, call number) PAIR in pinned host memory (store_words8_tagged: the host takes a word only
+// with this call's tag).  Workgroup 0 also publishes the flag words as pairs and zeroes them: this kernel ends the MSM, as k_reduce_bits does.
+__global__ void __launch_bounds__(64) k_g2_reduce_bits(const uint32_t* __restrict__ R, const uint32_t* __restrict__ C, uint32_t* __restrict__ q,
+                                                       uint32_t n_hi, uint32_t n_lo, uint32_t kb_lo, uint32_t kb, uint32_t* __restrict__ flags,
+                                                       uint32_t* __restrict__ flags_out, uint32_t seq) {
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        reinterpret_cast<uint2*>(flags_out)[threadIdx.x] = make_uint2(flags[threadIdx.x], seq);
+        flags[threadIdx.x] = 0;
+    }
+    const uint32_t w = blockIdx.x / (kb + 1), u = blockIdx.x % (kb + 1);
+    const uint32_t* src;
+    uint32_t cnt, bit;
+    if (u < kb_lo) {
+        src = C + (size_t)w * n_lo * XW2, cnt = n_lo, bit = u;
+    } else if (u < kb) {
+        src = R + (size_t)w * n_hi * XW2, cnt = n_hi, bit = u - kb_lo;
+    } else {
+        src = C + (size_t)w * n_lo * XW2, cnt = n_lo, bit = 0xFFFFFFFFu;
+    }
+    const uint32_t nsel = bit == 0xFFFFFFFFu ? cnt : cnt >> 1;
+    const uint32_t nser = (nsel + 63) / 64;
+    xyzz2 acc = xyzz2_identity();
+#pragma unroll 1
+    for (uint32_t step = 0; step < nser + 6; step++) {  // ONE addition call site: strided folds, then six shuffle levels
+        xyzz2 other = xyzz2_identity();
+        if (step < nser) {
+            const uint32_t m = threadIdx.x + 64 * step;
+            if (m < nsel) {
+                const uint32_t j = bit == 0xFFFFFFFFu ? m : (((m >> bit) << (bit + 1)) | (1u << bit) | (m & ((1u << bit) - 1u)));
+                other = load_xyzz2(src + (size_t)j * XW2);
+            }
+        } else {
+            const uint32_t d = 32u >> (step - nser);
+            if (d >= nsel) continue;  // uniform
+            const xyzz2 s{shfl_down_fp2(acc.x, d), shfl_down_fp2(acc.y, d), shfl_down_fp2(acc.zz, d), shfl_down_fp2(acc.zzz, d)};
+            if (threadIdx.x < d) other = s;  // lanes >= d take the identity (their own value would send them through the doubling)
+        }
+        acc = xyzz2_add(acc, other);
+    }
+    if (threadIdx.x == 0) {
+        // Jacobian without inversion: Z = ZZ * ZZZ, X' = X * ZZ^4, Y' = Y * ZZZ^4; the identity goes out as (1, 1, 0)
+        fp2 jx = fp2_one(), jy = fp2_one(), jz = fp2_zero();
+        if (!xyzz2_is_identity(acc)) {
+            const fp2 zz2 = fp2_sqr<6>(acc.zz), zzz2 = fp2_sqr<6>(acc.zzz);           // ZZ, ZZZ < 4.2: < 1.9
+            jx = fp2_mul<3>(acc.x, fp2_sqr<3>(zz2));                                   // (ZZ^2)^2 < 1.2;  X * () < 12 * 3.4k + 1 < 1.3
+            jy = fp2_mul<3>(acc.y, fp2_sqr<3>(zzz2));
+            jz = fp2_mul<6>(acc.zz, acc.zzz);
+        }
+        uint32_t* o = q + (size_t)blockIdx.x * 96;
+        auto put = [&](int c, const fp& v) {
+            uint32_t wds[8];
+            fp_to_mont256(wds, v);
+            store_words8_tagged(o + 16 * c, wds, seq);
+        };
+        put(0, jx.c0), put(1, jx.c1), put(2, jy.c0), put(3, jy.c1), put(4, jz.c0), put(5, jz.c1);
+    }
+}
+
+}  // namespace msmk

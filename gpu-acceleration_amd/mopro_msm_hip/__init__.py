@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "msm_multi_create", "msm_multi_destroy", "msm_multi_last_error", "msm_multi_num_devices", "msm_multi_exchange",
     "msm_bn254_g1_multi", "msm_bn254_g1_multi_arkworks", "msm_bn254_g1_multi_device", "msm_multi_get_timings",
     "msm_multi_get_exchange_stats", "msm_multi_get_exchange_probe",
+    "msm_bn254_g2", "msm_bn254_g2_device", "msm_bn254_g2_combine",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -139,6 +140,9 @@ def bind_product_abi(L):
     L.msm_multi_get_timings.argtypes = [vp, C.c_int32, C.POINTER(Timings)]
     L.msm_multi_get_exchange_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]
     L.msm_multi_get_exchange_probe.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.msm_bn254_g2.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, _u32p, _u32p, _u8p]
+    L.msm_bn254_g2_device.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, _u32p, _u32p, _u8p]
+    L.msm_bn254_g2_combine.argtypes = [_u32p, C.c_size_t, C.c_uint32, _u32p, _u32p, _u8p]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -194,6 +198,39 @@ class MsmResult:
             return None
         to_int = lambda ws: sum(int(w) << (32 * i) for i, w in enumerate(ws.tolist()))
         return to_int(self.affine_std[:8]), to_int(self.affine_std[8:])
+
+
+class G2Result:
+    """One G2 result: Jacobian Montgomery words X.c0 X.c1 Y.c0 Y.c1 Z.c0 Z.c1 (48) and the canonical affine standard-form words
+    x.c0 x.c1 y.c0 y.c1 (32)."""
+
+    def __init__(self, jac, aff, inf):
+        self.jacobian_mont = jac
+        self._aff = aff
+        self.is_infinity = bool(inf)
+
+    @property
+    def affine_std(self):
+        if self._aff is None:
+            self._aff = combine_partials_g2(self.jacobian_mont.reshape(1, 48))._aff
+        return self._aff
+
+    def affine_ints(self):
+        """((x.c0, x.c1), (y.c0, y.c1)) as Python integers, None for the identity"""
+        if self.is_infinity:
+            return None
+        w = [sum(int(v) << (32 * i) for i, v in enumerate(self.affine_std[8 * k:8 * k + 8].tolist())) for k in range(4)]
+        return (w[0], w[1]), (w[2], w[3])
+
+
+def combine_partials_g2(partials_jacobian_mont, want_affine=True, flags=0):
+    """Fold G2 partial sums (k x 48 Jacobian Montgomery words) in order on the host (msm_bn254_g2_combine); flags 0 or FLAG_DETERMINISTIC."""
+    p = _words(partials_jacobian_mont, 48)
+    jac, aff, inf = np.zeros(48, np.uint32), (np.zeros(32, np.uint32) if want_affine else None), C.c_uint8(0)
+    rc = load_library().msm_bn254_g2_combine(_p32(p), p.shape[0], flags, _p32(jac), _p32(aff), C.byref(inf))
+    if rc != OK:
+        raise MsmError(rc, "Empty input" if rc == ERR_EMPTY else f"G2 combine failed ({rc})")
+    return G2Result(jac, aff, inf.value)
 
 
 def plan(n, window_bits=0, flags=0, _lib=None):
@@ -404,6 +441,29 @@ class MsmContext:
                 self._check(rc)
             return MsmResult(self._jbuf.copy(), None, self._oi.value)  # affine words on demand (MsmResult.affine_std)
 
+    # -- BN254 G2 (the Groth16 B query) --------------------------------------------------------
+    def msm_g2(self, bases, scalars, form=FORM_STD, inf=None):
+        """bases: n x 32 words (x.c0, x.c1, y.c0, y.c1), scalars: n x 8 words standard form; lengths truncate to the shorter one as msm() does."""
+        bases, scalars = _words(bases, 32), _words(scalars, 8)
+        if bases.shape[0] == 0 or scalars.shape[0] == 0:
+            raise MsmError(ERR_EMPTY, "Empty input")
+        n = min(bases.shape[0], scalars.shape[0])
+        infp = None
+        if inf is not None:
+            inf = np.ascontiguousarray(inf, dtype=np.uint8)
+            infp = inf.ctypes.data_as(_u8p)
+        jac, aff, oi = np.zeros(48, np.uint32), np.zeros(32, np.uint32), C.c_uint8(0)
+        self._check(self._lib.msm_bn254_g2(self._h, _p32(bases), form, infp, _p32(scalars), n, _p32(jac), _p32(aff), C.byref(oi)))
+        return G2Result(jac, aff, oi.value)
+
+    def msm_g2_device(self, d_bases_ptr, d_scalars_ptr, n, d_inf_ptr=None, stream=None):
+        """All operands already in HBM (raw device pointers): bases n x 32 Montgomery words, scalars n x 8 words."""
+        if n == 0:
+            raise MsmError(ERR_EMPTY, "Empty input")
+        jac, oi = np.zeros(48, np.uint32), C.c_uint8(0)
+        self._check(self._lib.msm_bn254_g2_device(self._h, d_bases_ptr, d_inf_ptr, d_scalars_ptr, n, stream, _p32(jac), None, C.byref(oi)))
+        return G2Result(jac, None, oi.value)  # affine words on demand (G2Result.affine_std)
+
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))
 
@@ -548,6 +608,11 @@ def default_context():
 def hip_variable_base_msm(bases, scalars, form=FORM_STD, inf=None):
     """Drop-in for metal_variable_base_msm(&bases, &scalars) (metal_msm.rs:642-695)."""
     return default_context().msm(bases, scalars, form, inf)
+
+
+def hip_variable_base_msm_g2(bases, scalars, form=FORM_STD, inf=None):
+    """The G2 counterpart on the process-global context (the Groth16 B query)."""
+    return default_context().msm_g2(bases, scalars, form, inf)
 
 
 metal_variable_base_msm = hip_variable_base_msm  # the reference's own name, kept as an alias

@@ -265,6 +265,29 @@ int32_t msm_bn254_g1_combine(const uint32_t *partials_jacobian_mont, size_t k, u
 int32_t msm_bn254_g1_combine_flags(const uint32_t *partials_jacobian_mont, size_t k, uint32_t flags, uint32_t out_jacobian_mont[24],
                                    uint32_t out_affine_std[16], uint8_t *out_is_inf);
 
+/* ---- BN254 G2 (the Groth16 B query, sum w_i * B2_i): the twist y^2 = x^3 + 3/(9+u) over Fq2 = Fq[u]/(u^2+1) ------------------
+ * The same context, planner and flags as the G1 calls: MSM_FLAG_DETERMINISTIC, MSM_FLAG_NO_GLV (the split uses phi2(x, y) = (beta^2 x, y)),
+ * MSM_FLAG_UNSIGNED_DIGITS and window_bits are honoured; a scalar >= 2^254 fails the call with MSM_ERR_BAD_ARG and the context stays usable;
+ * msm_get_timings describes the last call.  No window table, resident set or batch form.
+ * bases_xy: n x 32 words (x.c0, x.c1, y.c0, y.c1; 8 words each), MSM_FORM_STD or MSM_FORM_MONT (= the words of ark_bn254 Fq2, R = 2^256);
+ *   the points are NOT validated: they must lie in G2 (what arkworks' G2Affine guarantees).
+ * inf_mask: n bytes or NULL; scalars: n x 8 words, standard form.
+ * out_jacobian_mont = X.c0 X.c1 Y.c0 Y.c1 Z.c0 Z.c1 (R = 2^256 Montgomery words; the identity is (1, 1, 0)), out_affine_std = x.c0 x.c1 y.c0 y.c1
+ *   in standard form (all zero for the identity); both nullable.  Errors as for msm_bn254_g1: MSM_ERR_EMPTY for n = 0, MSM_ERR_BAD_ARG for a NULL
+ *   pointer or a bad form; without a GPU no context exists (msm_ctx_create returns MSM_ERR_NO_DEVICE). */
+int32_t msm_bn254_g2(msm_ctx *ctx, const uint32_t *bases_xy, uint32_t base_form, const uint8_t *inf_mask,
+                     const uint32_t *scalars, size_t n, uint32_t out_jacobian_mont[48],
+                     uint32_t out_affine_std[32], uint8_t *out_is_inf);
+/* everything in HBM: d_bases_mont n x 32 words Montgomery form, d_inf_mask n bytes or NULL, d_scalars n x 8 words; hip_stream as for
+ * msm_bn254_g1_device.  Blocks until the result is on the host. */
+int32_t msm_bn254_g2_device(msm_ctx *ctx, const void *d_bases_mont, const void *d_inf_mask, const void *d_scalars,
+                            size_t n, void *hip_stream, uint32_t out_jacobian_mont[48],
+                            uint32_t out_affine_std[32], uint8_t *out_is_inf);
+/* host only, no GPU: fold k partials of 48 words (Jacobian Montgomery, as above) in order; flags 0 or MSM_FLAG_DETERMINISTIC (the Z = 1
+ * representative), any other bit MSM_ERR_BAD_ARG; k = 0 MSM_ERR_EMPTY. */
+int32_t msm_bn254_g2_combine(const uint32_t *partials_jacobian_mont, size_t k, uint32_t flags,
+                             uint32_t out_jacobian_mont[48], uint32_t out_affine_std[32], uint8_t *out_is_inf);
+
 /* ---- multi-GPU inside ONE process (the reference has no multi-device code: host/gpu.rs:3-5 opens the
  *      system default device).  The caller-facing signature is the same as the single-GPU calls; the point range is cut
  *      into `ndev` contiguous shards, device g pulls ITS OWN shard over its own PCIe link (one host thread + one context
