@@ -10,6 +10,7 @@
 //
 // Independent of oracle/ (which is test infrastructure and never linked into the product).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 
@@ -155,6 +156,11 @@ inline Jac jadd(const Jac& p, const Jac& q) {  // add-2007-bl, complete
     Fq z3 = dbl(mul(mul(p.z, q.z), h));
     return Jac{x3, y3, z3};
 }
+// the Z = 1 representative (Montgomery words); p must not be the identity
+inline Jac normalize(const Jac& p) {
+    const Fq zi = inv(p.z), zi2 = sqr(zi);
+    return Jac{mul(p.x, zi2), mul(p.y, mul(zi2, zi)), ONE};
+}
 // canonical affine, standard form; returns true for the identity (x = y = 0)
 inline bool to_affine_std(const Jac& p, Fq& x, Fq& y) {
     if (is_identity(p)) {
@@ -162,9 +168,9 @@ inline bool to_affine_std(const Jac& p, Fq& x, Fq& y) {
         y = x;
         return true;
     }
-    Fq zi = inv(p.z), zi2 = sqr(zi);
-    x = from_mont(mul(p.x, zi2));
-    y = from_mont(mul(p.y, mul(zi2, zi)));
+    const Jac a = normalize(p);
+    x = from_mont(a.x);
+    y = from_mont(a.y);
     return false;
 }
 inline Jac load_jac(const uint32_t* w) { return Jac{load_words(w), load_words(w + 8), load_words(w + 16)}; }
@@ -175,3 +181,21 @@ inline void store_jac(uint32_t* w, const Jac& p) {
 }
 
 }  // namespace hostg1
+
+// The group as the host finish sees it (host_finish.hpp): the point type, its C-ABI word counts and the operations on it.
+struct HostG1 {
+    using Jac = hostg1::Jac;
+    using F = hostg1::Fq;
+    static constexpr size_t JAC_WORDS = 24;  // X, Y, Z
+    static constexpr size_t AFF_WORDS = 16;  // x, y
+    static Jac identity() { return hostg1::identity(); }
+    static bool is_identity(const Jac& p) { return hostg1::is_identity(p); }
+    static Jac jdbl(const Jac& p) { return hostg1::jdbl(p); }
+    static Jac jadd(const Jac& p, const Jac& q) { return hostg1::jadd(p, q); }
+    static Jac normalize(const Jac& p) { return hostg1::normalize(p); }
+    static bool to_affine_std(const Jac& p, F& x, F& y) { return hostg1::to_affine_std(p, x, y); }
+    static F from_mont(const F& a) { return hostg1::from_mont(a); }
+    static Jac load_jac(const uint32_t* w) { return hostg1::load_jac(w); }
+    static void store_jac(uint32_t* w, const Jac& p) { hostg1::store_jac(w, p); }
+    static void store_words(uint32_t* w, const F& a) { hostg1::store_words(w, a); }
+};

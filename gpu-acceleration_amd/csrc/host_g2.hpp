@@ -1,6 +1,6 @@
 // host_g2.hpp -- host-side (CPU) BN254 G2 arithmetic of the PRODUCT: Fq2 = Fq[u] / (u^2 + 1) over hostg1::Fq (R = 2^256 Montgomery), Jacobian
 // addition / doubling on the twist (a = 0), affine conversion and the canonical Z = 1 form.  What finishes a G2 MSM after the GPU has produced its
-// bit sums (the Horner chain of host_finish, msm_hip.hip) and what msm_bn254_g2_combine folds with.
+// bit sums (the Horner chain of host_finish.hpp) and what msm_bn254_g2_combine folds with.
 //
 // C-ABI word order of an Fq2 element: c0 (8 words), c1 (8 words); of a Jacobian point: X.c0 X.c1 Y.c0 Y.c1 Z.c0 Z.c1 (48 words).
 #pragma once
@@ -100,3 +100,21 @@ inline void store_jac(uint32_t* w, const Jac& p) {
 }
 
 }  // namespace hostg2
+
+// The G2 counterpart of HostG1 (host_g1.hpp)
+struct HostG2 {
+    using Jac = hostg2::Jac;
+    using F = hostg2::Fq2;
+    static constexpr size_t JAC_WORDS = 48;  // X, Y, Z, each c0 c1
+    static constexpr size_t AFF_WORDS = 32;  // x, y
+    static Jac identity() { return hostg2::identity(); }
+    static bool is_identity(const Jac& p) { return hostg2::is_identity(p); }
+    static Jac jdbl(const Jac& p) { return hostg2::jdbl(p); }
+    static Jac jadd(const Jac& p, const Jac& q) { return hostg2::jadd(p, q); }
+    static Jac normalize(const Jac& p) { return hostg2::normalize(p); }
+    static bool to_affine_std(const Jac& p, F& x, F& y) { return hostg2::to_affine_std(p, x, y); }
+    static F from_mont(const F& a) { return hostg2::from_mont(a); }
+    static Jac load_jac(const uint32_t* w) { return hostg2::load_jac(w); }
+    static void store_jac(uint32_t* w, const Jac& p) { hostg2::store_jac(w, p); }
+    static void store_words(uint32_t* w, const F& a) { hostg2::store_words(w, a); }
+};

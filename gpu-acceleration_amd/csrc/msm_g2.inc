@@ -7,7 +7,7 @@
 //                                                                                            form so that it writes no G1 identity into the buckets]
 //   k_g2_clear_empty, k_g2_accumulate, k_g2_combine                                        [new]
 //   k_g2_pair_level x levels, k_g2_reduce_bits -> (word, call number) pairs in pinned memory [new]
-//   host_finish_group<HostG2> (Horner chain over the bit sums), outputs                     [G1's, templated]
+//   finish_sync<HostG2>: wait for the pairs, Horner chain over the bit sums, outputs        [G1's, templated]
 // The flag words, the call numbers (done_seq) and flags_clean are the context's, shared with G1 calls: the G2 reduction copies the flag words
 // out as pairs and zeroes them exactly as k_reduce_bits does.  No window table, no streaming, no multi-device form (follow-ups).
 
@@ -15,52 +15,13 @@ namespace {
 
 constexpr size_t XB2 = msmk::XW2 * 4;  // bytes per G2 XYZZ record
 
-struct HostG2 {
-    using Jac = hostg2::Jac;
-    static constexpr size_t WORDS = 48;
-    static Jac identity() { return hostg2::identity(); }
-    static Jac jdbl(const Jac& p) { return hostg2::jdbl(p); }
-    static Jac jadd(const Jac& p, const Jac& q) { return hostg2::jadd(p, q); }
-    static Jac load_jac(const uint32_t* w) { return hostg2::load_jac(w); }
-};
-
-// canonical = MSM_FLAG_DETERMINISTIC: the Z = 1 representative, the identity as (1, 1, 0) in Montgomery words -- as finish_outputs does for G1
-void finish_outputs_g2(const hostg2::Jac& r, uint32_t* out_jac, uint32_t* out_aff, uint8_t* out_inf, bool canonical) {
-    const bool ident = hostg2::is_identity(r);
-    if (out_inf) *out_inf = ident ? 1 : 0;
-    if (ident) {
-        if (out_jac) hostg2::store_jac(out_jac, hostg2::identity());
-        if (out_aff) std::memset(out_aff, 0, 128);
-        return;
-    }
-    if (!canonical && !out_aff) {
-        if (out_jac) hostg2::store_jac(out_jac, r);
-        return;
-    }
-    const hostg2::Jac a = hostg2::normalize(r);  // the one Fq2 inversion of the call
-    if (out_jac) hostg2::store_jac(out_jac, canonical ? a : r);
-    if (out_aff) {
-        hostg2::store_words(out_aff, hostg2::from_mont(a.x));
-        hostg2::store_words(out_aff + 16, hostg2::from_mont(a.y));
-    }
-}
-
-int32_t combine_partials_g2(const uint32_t* partials, size_t k, uint32_t* out_jac, uint32_t* out_aff, uint8_t* out_inf, bool canonical) {
-    if (!partials) return MSM_ERR_BAD_ARG;
-    if (k == 0) return MSM_ERR_EMPTY;
-    hostg2::Jac total = hostg2::identity();
-    for (size_t i = 0; i < k; i++) total = hostg2::jadd(total, hostg2::load_jac(partials + i * 48));  // fixed order
-    finish_outputs_g2(total, out_jac, out_aff, out_inf, canonical);
-    return MSM_OK;
-}
-
 // K4/K5 for G2: plain row / column sums by pairwise levels, then the per-bit sums straight into the pinned G2 result buffer
 int32_t enqueue_reduce_g2(msm_ctx* c, const PipeState& ps, hipStream_t st) {
     Range r_("msm:reduce_g2");
     const size_t tb = ps.tb;
     const uint32_t W = ps.rW, kb = ps.rkb, kb_lo = ps.kb_lo, kb_hi = ps.kb_hi, n_lo = ps.n_lo, n_hi = ps.n_hi;
-    uint32_t* rbuf[2] = {(uint32_t*)c->rc.p, (uint32_t*)c->rc.p + (tb / 2) * msmk::XW2};
-    uint32_t* cbuf[2] = {(uint32_t*)c->rc.p + (tb / 2 + tb / 4 + 1) * msmk::XW2, (uint32_t*)c->rc.p + (tb + tb / 4 + 1) * msmk::XW2};
+    uint32_t *rbuf[2], *cbuf[2];
+    reduce_bufs(c, tb, msmk::XW2, rbuf, cbuf);
     const uint32_t *rin = (const uint32_t*)c->buckets.p, *cin = rin;
     size_t rn = tb, cn = tb;
     const uint32_t levels = kb_hi > kb_lo ? kb_hi : kb_lo;
@@ -85,26 +46,6 @@ int32_t enqueue_reduce_g2(msm_ctx* c, const PipeState& ps, hipStream_t st) {
     msmk::k_g2_reduce_bits<<<W * (kb + 1), 64, 0, st>>>(rin, cin, q_dev, n_hi, n_lo, kb_lo, kb, (uint32_t*)c->flags.p, f_dev, c->done_seq);
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[EV_REDUCE], st));
     return MSM_OK;
-}
-
-// the G2 bit sums (48 words each) and the flag words out of their pairs, all tagged with this call's number (gather_results' rule)
-bool gather_results_g2(msm_ctx* c, uint32_t nblk, uint32_t seq) {
-    const volatile uint64_t* q64 = reinterpret_cast<const volatile uint64_t*>(c->h_qsums2);
-    const volatile uint64_t* f64 = reinterpret_cast<const volatile uint64_t*>(c->h_flags);
-    uint32_t* out = c->qsums2.data();
-    const size_t npairs = (size_t)nblk * 48;
-    for (size_t k = 0; k < npairs; k++) {
-        const uint64_t v = q64[k];
-        if ((uint32_t)(v >> 32) != seq) return false;
-        out[k] = (uint32_t)v;
-    }
-    for (int k = 0; k < 8; k++) {
-        const uint64_t v = f64[k];
-        if ((uint32_t)(v >> 32) != seq) return false;
-        c->flagw[k] = (uint32_t)v;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return true;
 }
 
 // The whole G2 pipeline on device-resident inputs: d_raw = n x 32 caller words (form), d_inf nullable, d_scalars n x 8 standard form.
@@ -150,53 +91,10 @@ int32_t run_g2(msm_ctx* c, const uint32_t* d_raw, uint32_t form, const uint8_t* 
         flags + msmk::FLAG_PAIRS);
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[EV_COMBINE], st));
     if ((rc = enqueue_reduce_g2(c, ps, st))) return rc;
-    // wait: poll the pairs, querying the stream every ~1000 polls so that a failed launch or a lost device ends the wait (finish_sync's rule)
-    const uint32_t nblk = ps.rW * (ps.rkb + 1), seq = c->done_seq;
-    if (c->stage_timing || c->knobs.no_poll) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (!gather_results_g2(c, nblk, seq)) return fail(c, MSM_ERR_HIP, "internal: the G2 bucket reduction finished without publishing its %u bit sums", nblk);
-    } else {
-        for (uint32_t spins = 1;; spins++) {
-            if (gather_results_g2(c, nblk, seq)) break;
-            if ((spins & 0x3FFu) == 0) {
-                const hipError_t q = hipStreamQuery(st);
-                if (q == hipSuccess) {
-                    if (gather_results_g2(c, nblk, seq)) break;
-                    return fail(c, MSM_ERR_HIP, "internal: the G2 bucket reduction finished without publishing its %u bit sums", nblk);
-                }
-                if (q != hipErrorNotReady) HIPCHK(c, q);
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    c->flags_clean = true;  // the last kernel zeroed the flag words after copying them out
-    const auto t_fin0 = std::chrono::steady_clock::now();
-    if ((rc = check_flags(c, c->flagw))) return rc == ARK_RETRY_SLOW ? fail(c, MSM_ERR_HIP, "internal: unexpected error bit 16") : rc;
-    const hostg2::Jac total = host_finish_group<HostG2>(c, c->qsums2.data(), ps);
-    finish_outputs_g2(total, out_jac, out_aff, out_inf, (c->cfg.flags & MSM_FLAG_DETERMINISTIC) != 0);
-    const auto t_fin1 = std::chrono::steady_clock::now();
-    float ms = 0;
-    msm_timings_t& tm = c->tm;
-    tm = msm_timings_t{};
-    tm.convert_ms = stage_ms(c, EV_H2D, EV_CONVERT);
-    tm.decompose_ms = stage_ms(c, EV_CONVERT, EV_DECOMP);
-    tm.sort_ms = stage_ms(c, EV_DECOMP, EV_SORT);
-    if (timed) {
-        (void)hipEventElapsedTime(&ms, c->ev[EV_ACC0], c->ev[EV_ACC1]);
-        c->acc_ms_sum += ms;
-        c->acc_launches += 1;
-    }
-    tm.accumulate_ms = ms;
-    tm.plan_ms = stage_ms(c, EV_SORT, EV_PLAN);
-    tm.combine_ms = stage_ms(c, EV_ACC1, EV_COMBINE);
-    tm.reduce_ms = stage_ms(c, EV_COMBINE, EV_REDUCE);
-    tm.batch_layout = c->last_batch_layout;
-    tm.finish_ms = std::chrono::duration<float, std::milli>(t_fin1 - t_fin0).count();
-    tm.num_points = n;
-    tm.num_adds = (uint64_t)c->flagw[msmk::FLAG_ADDS64] | ((uint64_t)c->flagw[msmk::FLAG_ADDS64 + 1] << 32);
+    rc = finish_sync<HostG2>(c, ps, n, st, out_jac, out_aff, out_inf);
+    if (rc == ARK_RETRY_SLOW) return fail(c, MSM_ERR_HIP, "internal: unexpected error bit 16");  // (a G1 struct-array call's bit)
+    if (rc) return rc;
+    c->tm.convert_ms = stage_ms(c, EV_H2D, EV_CONVERT);
     return MSM_OK;
 }
 
@@ -252,7 +150,7 @@ int32_t msm_bn254_g2_device(msm_ctx* c, const void* d_bases_mont, const void* d_
 
 int32_t msm_bn254_g2_combine(const uint32_t* partials, size_t k, uint32_t flags, uint32_t out_jac[48], uint32_t out_aff[32], uint8_t* out_inf) {
     if (flags & ~(uint32_t)MSM_FLAG_DETERMINISTIC) return MSM_ERR_BAD_ARG;
-    return combine_partials_g2(partials, k, out_jac, out_aff, out_inf, (flags & MSM_FLAG_DETERMINISTIC) != 0);
+    return combine_partials<HostG2>(partials, k, out_jac, out_aff, out_inf, (flags & MSM_FLAG_DETERMINISTIC) != 0);
 }
 
 }  // extern "C"

@@ -34,9 +34,11 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/msm_hip.h"
+#include "host_finish.hpp"
 #include "host_g1.hpp"
 #include "host_g2.hpp"
 #include "msm_host_pool.hpp"
@@ -299,46 +301,6 @@ float stage_ms(const msm_ctx* c, int a, int b) {
 
 inline dim3 grid1(size_t n, unsigned block) { return dim3((unsigned)((n + block - 1) / block)); }
 
-// canonical = MSM_FLAG_DETERMINISTIC: the Jacobian result is handed out as its Z = 1 representative (x*R, y*R, R), the identity as (R, R, 0)
-// -- the same 24 words for the same group element, whatever order the buckets were filled in (the sort places entries inside a bucket with
-// LDS atomics: the XYZZ sums, hence X : Y : Z, differ between identical calls; only the group element does not).  Costs the inversion the
-// affine output pays anyway (~10 us of host time), shared when both are asked for.
-void finish_outputs(const hostg1::Jac& r, uint32_t* out_jac, uint32_t* out_aff, uint8_t* out_inf, bool canonical = false) {
-    if (out_inf) *out_inf = hostg1::is_identity(r) ? 1 : 0;
-    if (canonical && out_jac) {
-        if (hostg1::is_identity(r)) {
-            hostg1::store_jac(out_jac, hostg1::identity());
-            if (out_aff) std::memset(out_aff, 0, 64);
-            return;
-        }
-        const hostg1::Fq zi = hostg1::inv(r.z), zi2 = hostg1::sqr(zi);
-        const hostg1::Fq xm = hostg1::mul(r.x, zi2), ym = hostg1::mul(r.y, hostg1::mul(zi2, zi));
-        hostg1::store_jac(out_jac, hostg1::Jac{xm, ym, hostg1::ONE});
-        if (out_aff) {
-            hostg1::store_words(out_aff, hostg1::from_mont(xm));
-            hostg1::store_words(out_aff + 8, hostg1::from_mont(ym));
-        }
-        return;
-    }
-    if (out_jac) hostg1::store_jac(out_jac, r);
-    if (out_aff) {  // the only inversion of the whole call (~10 us): callers that want the reference's result type
-                    // (Jacobian, metal_msm.rs:228-241) pass NULL and skip it
-        hostg1::Fq x, y;
-        (void)hostg1::to_affine_std(r, x, y);
-        hostg1::store_words(out_aff, x);
-        hostg1::store_words(out_aff + 8, y);
-    }
-}
-// msm_bn254_g1_combine with the representative chosen by the caller's flags (the multi-GPU fold of a MSM_FLAG_DETERMINISTIC handle)
-int32_t combine_partials(const uint32_t* partials, size_t k, uint32_t* out_jac, uint32_t* out_aff, uint8_t* out_inf, bool canonical) {
-    if (!partials) return MSM_ERR_BAD_ARG;
-    if (k == 0) return MSM_ERR_EMPTY;
-    hostg1::Jac total = hostg1::identity();
-    for (size_t i = 0; i < k; i++) total = hostg1::jadd(total, hostg1::load_jac(partials + i * 24));  // fixed rank order
-    finish_outputs(total, out_jac, out_aff, out_inf, canonical);
-    return MSM_OK;
-}
-
 // Everything the three enqueue steps of one (chunk of an) MSM share.  The PLAN (window width, digit form, GLV split: what the
 // bucket array looks like) is made for plan_n points -- the whole instance, also when only a chunk of it is sorted and
 // accumulated -- the sort geometry follows the points at hand.
@@ -353,9 +315,9 @@ struct PipeState {
     size_t sn = 0;
     uint32_t top_shift = 0;  // full table (tf == W): the short top window's digits enter as d * 2^top_shift (table_top_shift)
     uint32_t top_bits = 0;   // == pl.top_digit_bits: index bits of the top window that carry the digit; the kb - top_bits above it carry point-index
-                             // bits (split plans: msmplan::glv_top_digit_bits), which host_finish leaves out
+                             // bits (split plans: msmplan::glv_top_digit_bits), which host_finish_chain leaves out
     // REDUCTION view: arrays of more than 2^17 buckets are reduced as 2^pw_bits PSEUDO-windows of 2^rkb buckets each (bucket index
-    // b = q * 2^rkb + b'); the host adds q * 2^rkb * (plain sum of pseudo-window q) back in (host_finish).  rW = sW << pw_bits.
+    // b = q * 2^rkb + b'); the host adds q * 2^rkb * (plain sum of pseudo-window q) back in (host_finish_chain).  rW = sW << pw_bits.
     uint32_t rW = 0, rkb = 0, pw_bits = 0, kb_lo = 0, kb_hi = 0, n_lo = 0, n_hi = 0;
     size_t pairs = 0, tb = 0;  // sorted entries at most (= W * n = sW * sn), buckets in all (= sW * nb)
     // k_accumulate_pieces' work items: a whole bucket of at most pmax entries, or a run of psplit entries of a longer one
@@ -433,9 +395,17 @@ int32_t pipe_prepare(msm_ctx* c, size_t n_real, size_t plan_n, uint32_t extra_fl
     }
     // two lists: the two-piece buckets from entry 0 (at most tb of them), those of 3 .. LONG_SPAN-1 pieces from entry tb (piece_tally_publish)
     if ((rc = ensure(c, c->midlist, (tb + std::min(tb, maxpartials / 3) + 16) * 4))) return rc;
-    if ((rc = ensure(c, c->rc, (tb + tb / 2 + 4) * rec_bytes))) return rc;  // two families x (1/2 + 1/4) ping-pong levels
+    if ((rc = ensure(c, c->rc, (tb + tb / 2 + 4) * rec_bytes))) return rc;  // two families x (1/2 + 1/4) ping-pong levels: reduce_bufs
     if ((rc = ensure(c, c->flags, 64))) return rc;
     return MSM_OK;
+}
+
+// the bucket reduction's ping-pong buffers in c->rc (sized above) for tb buckets of rec_words words each: per family (rows, columns)
+// one level of tb/2 records, then one of tb/4 + 1
+void reduce_bufs(const msm_ctx* c, size_t tb, size_t rec_words, uint32_t* rbuf[2], uint32_t* cbuf[2]) {
+    uint32_t* base = (uint32_t*)c->rc.p;
+    rbuf[0] = base, rbuf[1] = base + (tb / 2) * rec_words;
+    cbuf[0] = base + (tb / 2 + tb / 4 + 1) * rec_words, cbuf[1] = base + (tb + tb / 4 + 1) * rec_words;
 }
 
 // the run length of very long buckets as the kernels take it (msmk::effective_psplit): the plan's psplit, the shift that shortens it for instances with few
@@ -717,9 +687,8 @@ int32_t enqueue_reduce(msm_ctx* c, const PipeState& ps, hipStream_t st, uint32_t
     const uint32_t W = ps.rW, kb = ps.rkb, kb_lo = ps.kb_lo, kb_hi = ps.kb_hi, n_lo = ps.n_lo, n_hi = ps.n_hi;
     uint32_t* flags = (uint32_t*)c->flags.p;
     const uint32_t* bk = (const uint32_t*)c->buckets.p;
-    // ping-pong buffers per family: [0, tb/2) and [tb/2, tb/2 + tb/4) elements
-    uint32_t* rbuf[2] = {(uint32_t*)c->rc.p, (uint32_t*)c->rc.p + (tb / 2) * msmk::XW};
-    uint32_t* cbuf[2] = {(uint32_t*)c->rc.p + (tb / 2 + tb / 4 + 1) * msmk::XW, (uint32_t*)c->rc.p + (tb + tb / 4 + 1) * msmk::XW};
+    uint32_t *rbuf[2], *cbuf[2];
+    reduce_bufs(c, tb, msmk::XW, rbuf, cbuf);
     const uint32_t *rin = bk, *cin = bk;
     size_t rn = tb, cn = tb;  // current element counts
     const uint32_t levels = kb_hi > kb_lo ? kb_hi : kb_lo;
@@ -792,73 +761,6 @@ int32_t enqueue_reduce(msm_ctx* c, const PipeState& ps, hipStream_t st, uint32_t
     return MSM_OK;
 }
 
-// final_reduction (metal_msm.rs:204-261) on the CPU.  The device returns, for every (pseudo-)window q of every bucket array v, the bit
-// sums Q_u (u < rkb: buckets whose index has bit u set) and the plain sum A.  With S_v = sum_b (b + 1) * B[v][b] and b = q * 2^rkb + b'
-//     S_v = sum_q [ A_q + sum_u 2^u Q_q,u ]  +  2^rkb * sum_q q * A_q          (second term: arrays cut into pseudo-windows only)
-// and the result is sum_v 2^(cbits * tf * v) S_v (tf windows share an array with a window table, tf = 1 without): ONE Horner chain
-// over the bit positions p = cbits*tf*v + u with the terms
-//     u < rkb:  sum_q Q_q,u   (+ sum_q A_q at u == 0);      rkb <= u < kb:  sum over {q : bit u-rkb of q set} of A_q
-// (one doubling and about one addition per position) instead of the reference's chain per window plus c doublings between windows
-// (metal_msm.rs:249-258).  The chain is cut into a few segments of geometrically shrinking length (a segment starting at position
-// lo pays lo extra doublings to shift its sum), one per host thread: 2 threads reach ~60 % of the serial time, 4 threads ~45 %, more
-// add nothing because the shift of the top segment is serial.  TWO threads by default: every further worker lowers the median by a
-// few microseconds and raises the MEAN through 2-8 ms outliers in ~1.3 % of the calls (busy hosts; a pool of 15: 2.5 %) --
-// tools/step_jitter.py.  With one shared bucket array (full window table) the chain is cbits - 1 positions long instead of 254.
-// The group is a template argument (G1: HostG1 below, G2: HostG2 in msm_g2.inc): the bit sums are G::WORDS words each.
-struct HostG1 {
-    using Jac = hostg1::Jac;
-    static constexpr size_t WORDS = 24;
-    static Jac identity() { return hostg1::identity(); }
-    static Jac jdbl(const Jac& p) { return hostg1::jdbl(p); }
-    static Jac jadd(const Jac& p, const Jac& q) { return hostg1::jadd(p, q); }
-    static Jac load_jac(const uint32_t* w) { return hostg1::load_jac(w); }
-};
-template <class G>
-typename G::Jac host_finish_group(msm_ctx* c, const uint32_t* h_qsums, const PipeState& g) {
-    Range r_("msm:host_finish");
-    using Jac = typename G::Jac;
-    const uint32_t V = g.sW, kb = g.kb, rkb = g.rkb, PW = 1u << g.pw_bits, spacing = g.cbits * g.tf;
-    const uint32_t npos = spacing * (V - 1) + (kb > 0 ? kb : 1);  // positions 0 .. npos-1 carry terms
-    auto qsum = [&](uint32_t v, uint32_t q, uint32_t u) { return G::load_jac(h_qsums + ((size_t)(v * PW + q) * (rkb + 1) + u) * G::WORDS); };
-    auto segment = [&](uint32_t lo, uint32_t hi) {             // sum over p in [lo, hi) of 2^p * term(p)
-        Jac acc = G::identity();
-        for (uint32_t p = hi; p-- > lo;) {
-            acc = G::jdbl(acc);
-            const uint32_t v = p / spacing, u = p % spacing;
-            if (v == V - 1 && u >= g.top_bits) {
-                // index bits of a spread top window that hold point-index bits, not the digit (msmplan::glv_top_digit_bits): no weight
-            } else if (u < rkb)
-                for (uint32_t q = 0; q < PW; q++) acc = G::jadd(acc, qsum(v, q, u));
-            else if (u < kb)
-                for (uint32_t q = 0; q < PW; q++)
-                    if ((q >> (u - rkb)) & 1u) acc = G::jadd(acc, qsum(v, q, rkb));
-            if (u == 0)
-                for (uint32_t q = 0; q < PW; q++) acc = G::jadd(acc, qsum(v, q, rkb));
-        }
-        for (uint32_t k = 0; k < lo; k++) acc = G::jdbl(acc);
-        return acc;
-    };
-    const int nseg = c->pool ? std::min<int>(c->pool->size() + 1, 8) : 1;
-    if (nseg == 1 || npos < 16) return segment(0, npos);
-    // segment k has length proportional to 0.7^k (a doubling costs ~0.3 of a position's doubling + addition)
-    uint32_t bound[9];
-    double tot = 0, wgt = 1;
-    for (int k = 0; k < nseg; k++, wgt *= 0.7) tot += wgt;
-    double run = 0;
-    wgt = 1;
-    bound[0] = 0;
-    for (int k = 0; k < nseg; k++, wgt *= 0.7) {
-        run += wgt;
-        bound[k + 1] = k + 1 == nseg ? npos : (uint32_t)(npos * (run / tot) + 0.5);
-    }
-    std::vector<Jac> part((size_t)nseg);
-    c->pool->run(nseg, [&](int k) { part[(size_t)k] = segment(bound[k], bound[k + 1]); });  // job 0 (the longest) is taken first
-    Jac total = part[0];
-    for (int k = 1; k < nseg; k++) total = G::jadd(total, part[(size_t)k]);
-    return total;
-}
-hostg1::Jac host_finish(msm_ctx* c, const uint32_t* h_qsums, const PipeState& g) { return host_finish_group<HostG1>(c, h_qsums, g); }
-
 constexpr int32_t ARK_RETRY_SLOW = 1;  // (internal, never handed out: see KIND_ARKFAST)
 int32_t check_flags(msm_ctx* c, const uint32_t* h_flags) {
     if (h_flags[0] & 1u) return fail(c, MSM_ERR_BAD_ARG, "a scalar is >= 2^254 (not a canonical Fr element)");
@@ -880,14 +782,22 @@ void trace_line(const msm_ctx* c, const char* entry, const PipeState& ps) {
                  c->enqueue_ms, (unsigned long long)t.num_adds);
 }
 
+// A group's bit sums as the last kernel writes them (pinned (word, call number) pairs) and as the call being finished took them out:
+// c->h_qsums / c->qsums for G1 calls, c->h_qsums2 / c->qsums2 for G2 calls
+template <class G>
+uint32_t* pinned_qsums(msm_ctx* c) { return std::is_same<G, HostG2>::value ? c->h_qsums2 : c->h_qsums; }
+template <class G>
+std::vector<uint32_t>& taken_qsums(msm_ctx* c) { return std::is_same<G, HostG2>::value ? c->qsums2 : c->qsums; }
+
 // The last kernel's results out of pinned memory: every word arrives as an aligned 8-byte (word, sequence number) pair written by ONE device store and read
 // here by ONE load, so a word is taken only with the tag of THIS call (msm_kernels.hpp, store_words8_tagged: why a sequence word behind a fence was not enough).
 // false: some pair is not there yet (nothing is half-taken: the caller polls on, or reports an error when the kernel has retired).
+template <class G>
 bool gather_results(msm_ctx* c, uint32_t nblk, uint32_t seq) {
-    const volatile uint64_t* q64 = reinterpret_cast<const volatile uint64_t*>(c->h_qsums);
+    const volatile uint64_t* q64 = reinterpret_cast<const volatile uint64_t*>(pinned_qsums<G>(c));
     const volatile uint64_t* f64 = reinterpret_cast<const volatile uint64_t*>(c->h_flags);
-    uint32_t* out = c->qsums.data();
-    const size_t npairs = (size_t)nblk * 24;
+    uint32_t* out = taken_qsums<G>(c).data();
+    const size_t npairs = (size_t)nblk * G::JAC_WORDS;
     for (size_t k = 0; k < npairs; k++) {
         const uint64_t v = q64[k];
         if ((uint32_t)(v >> 32) != seq) return false;
@@ -903,8 +813,11 @@ bool gather_results(msm_ctx* c, uint32_t nblk, uint32_t seq) {
 }
 
 // wait for the queued pipeline, finish on the CPU, fill outputs and timings
+template <class G>
 int32_t finish_sync(msm_ctx* c, const PipeState& ps, size_t n_total, hipStream_t st, uint32_t* out_jac, uint32_t* out_aff, uint8_t* out_inf,
                     hipEvent_t done = nullptr /* recorded after the last kernel when `st` carries other work too */) {
+    constexpr uint32_t JW = (uint32_t)G::JAC_WORDS;
+    const std::vector<uint32_t>& qsums = taken_qsums<G>(c);
     if (trace_enabled()) c->enqueue_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c->t_prepare).count();
     if (c->pool && n_total >= 256) c->pool->arm();  // workers wake up while the GPU works
     // Round 6: the host polls the results themselves -- (word, call number) pairs the last kernel's workgroups write into pinned memory (gather_results) -- instead of
@@ -915,18 +828,18 @@ int32_t finish_sync(msm_ctx* c, const PipeState& ps, size_t n_total, hipStream_t
     if (c->stage_timing || c->knobs.no_poll) {
         if (done) HIPCHK(c, hipEventSynchronize(done));
         else HIPCHK(c, hipStreamSynchronize(st));
-        if (!gather_results(c, nblk, seq)) return fail(c, MSM_ERR_HIP, "internal: the bucket reduction finished without publishing its %u bit sums", nblk);
+        if (!gather_results<G>(c, nblk, seq)) return fail(c, MSM_ERR_HIP, "internal: the bucket reduction finished without publishing its %u bit sums", nblk);
     } else {
         // cheap test first: the LAST pair of every bit sum; then every pair (a pair that is not there yet: keep polling)
-        const volatile uint64_t* q64 = reinterpret_cast<const volatile uint64_t*>(c->h_qsums);
+        const volatile uint64_t* q64 = reinterpret_cast<const volatile uint64_t*>(pinned_qsums<G>(c));
         for (uint32_t spins = 1;; spins++) {
             uint32_t i = 0;
-            while (i < nblk && (uint32_t)(q64[(size_t)i * 24 + 23] >> 32) == seq) i++;
-            if (i == nblk && gather_results(c, nblk, seq)) break;
+            while (i < nblk && (uint32_t)(q64[(size_t)i * JW + JW - 1] >> 32) == seq) i++;
+            if (i == nblk && gather_results<G>(c, nblk, seq)) break;
             if ((spins & 0x3FFu) == 0) {
                 const hipError_t q = done ? hipEventQuery(done) : hipStreamQuery(st);
                 if (q == hipSuccess) {  // retired: the pairs must be there now
-                    if (gather_results(c, nblk, seq)) break;
+                    if (gather_results<G>(c, nblk, seq)) break;
                     return fail(c, MSM_ERR_HIP, "internal: the bucket reduction finished without publishing its %u bit sums", nblk);
                 }
                 if (q != hipErrorNotReady) HIPCHK(c, q);
@@ -937,15 +850,15 @@ int32_t finish_sync(msm_ctx* c, const PipeState& ps, size_t n_total, hipStream_t
         }
 #ifdef MSM_HIP_TEST_HOOKS
         if (std::getenv("MSM_HIP_POLL_VERIFY")) {  // diagnosis (tools/race_hunt.py): is what the host accepted what the RETIRED kernel left?
-            const std::vector<uint32_t> snap(c->qsums.begin(), c->qsums.begin() + (size_t)nblk * 24);
+            const std::vector<uint32_t> snap(qsums.begin(), qsums.begin() + (size_t)nblk * JW);
             uint32_t fl[8];
             std::memcpy(fl, c->flagw, sizeof fl);
             if (done) HIPCHK(c, hipEventSynchronize(done));
             else HIPCHK(c, hipStreamSynchronize(st));
-            if (!gather_results(c, nblk, seq)) return fail(c, MSM_ERR_HIP, "internal: POLL_VERIFY: pairs missing after the kernel retired");
-            for (uint32_t k = 0; k < nblk * 24; k++)
-                if (snap[k] != c->qsums[k]) {
-                    std::fprintf(stderr, "[msm_hip] POLL_VERIFY: bit sum %u word %u accepted as %08x, is %08x (seq %u, %u sums)\n", k / 24, k % 24, snap[k], c->qsums[k], seq, nblk);
+            if (!gather_results<G>(c, nblk, seq)) return fail(c, MSM_ERR_HIP, "internal: POLL_VERIFY: pairs missing after the kernel retired");
+            for (uint32_t k = 0; k < nblk * JW; k++)
+                if (snap[k] != qsums[k]) {
+                    std::fprintf(stderr, "[msm_hip] POLL_VERIFY: bit sum %u word %u accepted as %08x, is %08x (seq %u, %u sums)\n", k / JW, k % JW, snap[k], qsums[k], seq, nblk);
                     break;
                 }
             if (std::memcmp(fl, c->flagw, sizeof fl)) std::fprintf(stderr, "[msm_hip] POLL_VERIFY: flag words accepted early differ\n");
@@ -957,8 +870,12 @@ int32_t finish_sync(msm_ctx* c, const PipeState& ps, size_t n_total, hipStream_t
     auto t_fin0 = std::chrono::steady_clock::now();
     int32_t rc;
     if ((rc = check_flags(c, c->flagw))) return rc;
-    hostg1::Jac total = host_finish(c, c->qsums.data(), ps);
-    finish_outputs(total, out_jac, out_aff, out_inf, (c->cfg.flags & MSM_FLAG_DETERMINISTIC) != 0);
+    typename G::Jac total;
+    {
+        Range r_("msm:host_finish");
+        total = host_finish_chain<G>(qsums.data(), ps.sW, ps.kb, ps.rkb, ps.pw_bits, ps.cbits * ps.tf, ps.top_bits, c->pool);
+    }
+    finish_outputs<G>(total, out_jac, out_aff, out_inf, (c->cfg.flags & MSM_FLAG_DETERMINISTIC) != 0);
     auto t_fin1 = std::chrono::steady_clock::now();
     float ms = 0;
     msm_timings_t& tm = c->tm;
@@ -1022,7 +939,7 @@ int32_t run_pipeline(msm_ctx* c, const BaseSrc& d_bases, const uint8_t* d_inf, c
         }
         if ((rc = enqueue_reduce(c, ps, st, c->h_qsums, c->h_flags))) return rc;
         if (ps_out) *ps_out = ps;
-        if ((rc = finish_sync(c, ps, n, st, out_jac, out_aff, out_inf))) return rc;
+        if ((rc = finish_sync<HostG1>(c, ps, n, st, out_jac, out_aff, out_inf))) return rc;
         c->tm.stream_chunks = nch;
         return MSM_OK;
     }
@@ -1030,7 +947,7 @@ int32_t run_pipeline(msm_ctx* c, const BaseSrc& d_bases, const uint8_t* d_inf, c
     if ((rc = enqueue_body(c, ps, d_bases, d_inf, d_scalars, scalars_mont, st, bases_ready))) return rc;
     if ((rc = enqueue_reduce(c, ps, st, c->h_qsums, c->h_flags))) return rc;
     if (ps_out) *ps_out = ps;
-    return finish_sync(c, ps, n, st, out_jac, out_aff, out_inf);
+    return finish_sync<HostG1>(c, ps, n, st, out_jac, out_aff, out_inf);
 }
 
 struct DeviceGuard {
@@ -1187,7 +1104,7 @@ int32_t run_single(msm_ctx* c, const HostInput& in, size_t n, uint32_t* out_jac,
         }
     }
     if ((rc = enqueue_reduce(c, ps, st, c->h_qsums, c->h_flags))) return rc;
-    if ((rc = finish_sync(c, ps, n, st, out_jac, out_aff, out_inf))) return rc;
+    if ((rc = finish_sync<HostG1>(c, ps, n, st, out_jac, out_aff, out_inf))) return rc;
     c->tm.h2d_ms = stage_ms(c, EV_START, EV_H2D);
     c->tm.convert_ms = stage_ms(c, EV_H2D, EV_CONVERT);
     trace_line(c, "host single-shot", ps);
@@ -1253,7 +1170,7 @@ int32_t run_streamed(msm_ctx* c, const HostInput& in, size_t n, const std::vecto
         lo += cnt;
     }
     if ((rc = enqueue_reduce(c, ps, st, c->h_qsums, c->h_flags))) return rc;
-    if ((rc = finish_sync(c, ps, n, st, out_jac, out_aff, out_inf))) return rc;
+    if ((rc = finish_sync<HostG1>(c, ps, n, st, out_jac, out_aff, out_inf))) return rc;
     c->tm.stream_chunks = (uint32_t)sizes.size();
     trace_line(c, "host streamed", ps);
     return MSM_OK;
@@ -1825,7 +1742,7 @@ static int32_t resident_on_lane(msm_ctx* w, const msm_ctx* owner, const uint32_t
             if ((rc = enqueue_reduce(w, ps, rs, w->h_qsums, w->h_flags))) return rc;
             if (shared) HIPCHK(w, hipEventRecord(w->ev_bases, rs));
         }
-        if ((rc = finish_sync(w, ps, n, st, out_jac, out_aff, out_inf, shared ? w->ev_bases : nullptr))) return rc;
+        if ((rc = finish_sync<HostG1>(w, ps, n, st, out_jac, out_aff, out_inf, shared ? w->ev_bases : nullptr))) return rc;
     }
     w->tm.h2d_ms = stage_ms(w, EV_START, EV_H2D);
     w->tm.convert_ms = 0;
@@ -2002,13 +1919,13 @@ int32_t msm_bn254_g1_device(msm_ctx* c, const void* d_bases_mont, const void* d_
 
 int32_t msm_bn254_g1_combine(const uint32_t* partials, size_t k, uint32_t out_jac[24], uint32_t out_aff[16],
                              uint8_t* out_inf) {
-    return combine_partials(partials, k, out_jac, out_aff, out_inf, false);
+    return combine_partials<HostG1>(partials, k, out_jac, out_aff, out_inf, false);
 }
 
 int32_t msm_bn254_g1_combine_flags(const uint32_t* partials, size_t k, uint32_t flags, uint32_t out_jac[24], uint32_t out_aff[16],
                                    uint8_t* out_inf) {
     if (flags & ~(uint32_t)MSM_FLAG_DETERMINISTIC) return MSM_ERR_BAD_ARG;
-    return combine_partials(partials, k, out_jac, out_aff, out_inf, (flags & MSM_FLAG_DETERMINISTIC) != 0);
+    return combine_partials<HostG1>(partials, k, out_jac, out_aff, out_inf, (flags & MSM_FLAG_DETERMINISTIC) != 0);
 }
 
 int32_t msm_plan(size_t n, uint32_t window_bits, uint32_t flags, msm_plan_t* out) {

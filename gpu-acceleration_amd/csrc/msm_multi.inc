@@ -236,10 +236,10 @@ int32_t multi_run(msm_multi* m, const std::vector<size_t>& cnt, F&& local, uint3
             for (int g = 1; g < G; g++)
                 if (std::memcmp(&m->folded[0], &m->folded[(size_t)g * 24], 96) != 0)
                     return mfail(m, MSM_ERR_RCCL, "rank %d holds a different result than rank 0 after the all-gather", g);
-        return combine_partials(&m->folded[0], 1, out_jac, out_aff, out_inf, canonical);
+        return combine_partials<HostG1>(&m->folded[0], 1, out_jac, out_aff, out_inf, canonical);
     }
     const auto tx = std::chrono::steady_clock::now();
-    const int32_t rc = combine_partials(m->partial.data(), (size_t)G, out_jac, out_aff, out_inf, canonical);  // host fold, rank order
+    const int32_t rc = combine_partials<HostG1>(m->partial.data(), (size_t)G, out_jac, out_aff, out_inf, canonical);  // host fold, rank order
     m->exchange_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tx).count();
     return rc;
 }

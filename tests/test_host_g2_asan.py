@@ -1,5 +1,5 @@
-"""HOST-only AddressSanitizer + UBSan build of host_g2.hpp (the CPU side of the G2 MSM: partial folds, the Horner chain's group operations,
-affine conversion): tools/host_g2_asan_check.cpp, `make -C gpu-acceleration_amd/csrc asan-g2`.  Known answers come from the group itself."""
+"""HOST-only AddressSanitizer + UBSan build of host_g2.hpp and the G2 finish of host_finish.hpp (the CPU side of the G2 MSM: partial folds,
+the Horner chain, affine conversion): tools/host_g2_asan_check.cpp, `make -C gpu-acceleration_amd/csrc asan-g2`.  Known answers come from the group itself."""
 import os
 import shutil
 import subprocess

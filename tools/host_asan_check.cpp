@@ -1,6 +1,7 @@
 // tools/host_asan_check.cpp -- HOST-only AddressSanitizer + UBSan build of the parts of the host runtime that need no GPU
 // (SURVEY.md section 5 "sanitizer host build"; GPU ASan is not available on this pool): the planner (msm_planner.hpp), the thread pool
-// (msm_host_pool.hpp), the CPU finish arithmetic (host_g1.hpp), the host side of the GLV split (glv_bn254.hpp) and the shard /
+// (msm_host_pool.hpp), the CPU finish arithmetic (host_g1.hpp) and the G1 finish itself (host_finish.hpp: the Horner chain over the bit
+// sums, the fold of partials and the outputs -- tools/host_finish_check.hpp), the host side of the GLV split (glv_bn254.hpp) and the shard /
 // chunk-schedule arithmetic.  Built by `make -C gpu-acceleration_amd/csrc asan`, run by tests/test_host_asan.py.
 #include <atomic>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include "../gpu-acceleration_amd/csrc/host_g1.hpp"
 #include "../gpu-acceleration_amd/csrc/msm_host_pool.hpp"
 #include "../gpu-acceleration_amd/csrc/msm_planner.hpp"
+#include "host_finish_check.hpp"
 
 #define REQUIRE(c)                                                              \
     do {                                                                        \
@@ -138,7 +140,7 @@ static int check_g1() {
         Fq one = mul(a, inv(a));
         REQUIRE(std::memcmp(one.l, ONE.l, 32) == 0);
     }
-    return 0;
+    return finishcheck::check_chain<HostG1>(g, "G1") + finishcheck::check_combine<HostG1>(g, "G1");
 }
 
 static int check_glv() {
@@ -296,6 +298,6 @@ static int check_piece_plan() {
 
 int main() {
     if (check_planner() || check_table_planner() || check_piece_plan() || check_pool() || check_g1() || check_glv() || check_partitions()) return 1;
-    std::puts("host runtime: planner, window-table planner, piece plan, pool, host_g1, glv split, partitions clean under ASan/UBSan");
+    std::puts("host runtime: planner, window-table planner, piece plan, pool, host_g1, G1 finish, glv split, partitions clean under ASan/UBSan");
     return 0;
 }

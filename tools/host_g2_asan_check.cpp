@@ -1,13 +1,16 @@
-// HOST-only AddressSanitizer + UBSan check of host_g2.hpp (the G2 arithmetic that finishes and folds G2 MSMs): `make -C gpu-acceleration_amd/csrc
-// asan-g2`, run by tests/test_host_g2_asan.py.  Fixed inputs, known answers derived inside the group (k * G by double-and-add):
-//   * partial folds as msm_bn254_g2_combine does them (k = 1, 2, 5; the identity, P + (-P), P + P), on Jacobian representatives with Z != 1;
-//   * a Horner chain sum_u 2^u * (c_u G) -- the shape of the CPU finish over the bit sums -- against (sum_u 2^u c_u) * G;
+// HOST-only AddressSanitizer + UBSan check of host_g2.hpp (the G2 arithmetic that finishes and folds G2 MSMs) and of the G2 finish itself
+// (host_finish.hpp): `make -C gpu-acceleration_amd/csrc asan-g2`, run by tests/test_host_g2_asan.py.  Fixed inputs, known answers derived
+// inside the group (k * G by double-and-add):
+//   * partial folds through combine_partials<HostG2>, as msm_bn254_g2_combine runs them (k = 1, 2, 5; the identity, P + (-P), P + P), on
+//     Jacobian representatives with Z != 1, and its outputs (tools/host_finish_check.hpp);
+//   * the Horner chain of the CPU finish, host_finish_chain<HostG2>, over bit sums of several shapes (tools/host_finish_check.hpp);
 //   * affine conversion of the results onto the twist y^2 = x^3 + 3/(9+u).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "host_g2.hpp"
+#include "../../tools/host_finish_check.hpp"
 
 using hostg1::Fq;
 using namespace hostg2;
@@ -31,19 +34,8 @@ static Fq fq_hex(const char* h) {  // 64 hex digits, big-endian
     }
     return hostg1::to_mont(r);
 }
-static bool same_point(const Jac& a, const Jac& b) {
-    if (is_identity(a) || is_identity(b)) return is_identity(a) && is_identity(b);
-    const Jac na = normalize(a), nb = normalize(b);
-    return std::memcmp(&na, &nb, sizeof na) == 0;
-}
-static Jac smul(const Jac& p, uint64_t k) {
-    Jac acc = identity(), base = p;
-    for (; k; k >>= 1) {
-        if (k & 1) acc = jadd(acc, base);
-        base = jdbl(base);
-    }
-    return acc;
-}
+static bool same_point(const Jac& a, const Jac& b) { return finishcheck::same_point<HostG2>(a, b); }
+static Jac smul(const Jac& p, uint64_t k) { return finishcheck::smul<HostG2>(p, k); }
 static Jac rescale(const Jac& p, const Fq2& z) {  // the same point with Z multiplied by z
     const Fq2 z2 = sqr(z);
     return Jac{mul(p.x, z2), mul(p.y, mul(z2, z)), mul(p.z, z)};
@@ -68,12 +60,15 @@ int main() {
     CHECK(on_twist(G), "generator on the twist");
     const Fq2 z1{hostg1::to_mont(Fq{{12345, 0, 0, 0}}), hostg1::to_mont(Fq{{678, 1, 0, 0}})};
     const Fq2 z2{hostg1::to_mont(Fq{{99, 0, 7, 0}}), hostg1::to_mont(Fq{{5, 0, 0, 3}})};
-    // folds of partials through their 48-word images, as msm_bn254_g2_combine reads them
+    // folds of partials through their 48-word images, by msm_bn254_g2_combine's code
     auto fold = [](const std::vector<Jac>& parts) {
         std::vector<uint32_t> w(parts.size() * 48);
         for (size_t i = 0; i < parts.size(); i++) store_jac(w.data() + 48 * i, parts[i]);
-        Jac t = identity();
-        for (size_t i = 0; i < parts.size(); i++) t = jadd(t, load_jac(w.data() + 48 * i));
+        uint32_t out[48];
+        uint8_t inf = 2;
+        CHECK(combine_partials<HostG2>(w.data(), parts.size(), out, nullptr, &inf, false) == MSM_OK, "combine_partials<HostG2>");
+        const Jac t = load_jac(out);
+        CHECK(inf == (is_identity(t) ? 1 : 0), "out_inf");
         return t;
     };
     const Jac p5 = smul(G, 5), p7 = smul(G, 7);
@@ -84,20 +79,11 @@ int main() {
     CHECK(is_identity(fold({rescale(p5, z2), neg5})), "P + (-P)");
     CHECK(same_point(fold({rescale(p7, z1), rescale(p7, z2)}), smul(G, 14)), "P + P through jadd");
     CHECK(same_point(jdbl(p7), smul(G, 14)), "jdbl");
-    // Horner chain over 40 positions with small multiples as the terms
-    Jac acc = identity();
-    uint64_t want = 0;
-    for (int u = 39; u >= 0; u--) {
-        acc = jdbl(acc);
-        const uint64_t c = (uint64_t)((u * 7 + 3) % 5);
-        if (c) acc = jadd(acc, rescale(smul(G, c), u & 1 ? z1 : z2));
-        want += c << u;
-    }
-    CHECK(same_point(acc, smul(G, want)), "Horner chain");
-    CHECK(on_twist(acc), "chain result on the twist");
+    CHECK(on_twist(fold({rescale(p5, z1), rescale(p7, z2)})), "fold result on the twist");
+    failures += finishcheck::check_chain<HostG2>(G, "G2") + finishcheck::check_combine<HostG2>(G, "G2");
     Fq2 x, y;
     CHECK(to_affine_std(identity(), x, y) && is_zero(x) && is_zero(y), "identity -> (0, 0)");
     if (failures) return 1;
-    std::printf("host_g2.hpp: folds, Horner chain, affine conversion -- clean under ASan/UBSan\n");
+    std::printf("host_g2.hpp: folds, Horner chain, combine outputs, affine conversion -- clean under ASan/UBSan\n");
     return 0;
 }
