@@ -99,6 +99,31 @@ inline void store_jac(uint32_t* w, const Jac& p) {
     store_words(w + 32, p.z);
 }
 
+// 64-byte image of ark-serialize 0.4 G2Affine::serialize_compressed (msm_bn254_g2_compress): x.c0 | x.c1, 32 bytes each, little-endian standard
+// form; byte 63 bit 7 = y is the larger of (y, -y), bit 6 = the point at infinity (then everything else is zero).  ark-ff 0.4 orders a quadratic
+// extension by c1 first, then c0, each as a standard-form integer: y > -y <=> y.c1 > (p-1)/2, or y.c1 == 0 and y.c0 > (p-1)/2 (0 is not larger).
+// xy: 32 words x.c0 x.c1 y.c0 y.c1 (mont: R = 2^256 Montgomery words, else standard form).
+inline void compress_point(const uint32_t* xy, bool mont, bool infinity, uint8_t out[64]) {
+    static constexpr uint64_t HALF[4] = {0x9e10460b6c3e7ea3ULL, 0xcbc0b548b438e546ULL, 0xdc2822db40c0ac2eULL, 0x183227397098d014ULL};  // (p-1)/2
+    uint32_t w[16] = {};
+    if (infinity) {
+        w[15] = 1u << 30;
+    } else {
+        Fq2 x = load_words(xy), y = load_words(xy + 16);
+        if (mont) x = from_mont(x), y = from_mont(y);
+        store_words(w, x);
+        const Fq& key = hostg1::is_zero(y.c1) ? y.c0 : y.c1;
+        bool larger = false;
+        for (int k = 3; k >= 0; k--)
+            if (key.l[k] != HALF[k]) {
+                larger = key.l[k] > HALF[k];
+                break;
+            }
+        if (larger) w[15] |= 1u << 31;
+    }
+    std::memcpy(out, w, 64);
+}
+
 }  // namespace hostg2
 
 // The G2 counterpart of HostG1 (host_g1.hpp)

@@ -9,7 +9,8 @@
 //   k_g2_pair_level x levels, k_g2_reduce_bits -> (word, call number) pairs in pinned memory [new]
 //   finish_sync<HostG2>: wait for the pairs, Horner chain over the bit sums, outputs        [G1's, templated]
 // The flag words, the call numbers (done_seq) and flags_clean are the context's, shared with G1 calls: the G2 reduction copies the flag words
-// out as pairs and zeroes them exactly as k_reduce_bits does.  No window table, no streaming, no multi-device form (follow-ups).
+// out as pairs and zeroes them exactly as k_reduce_bits does.  No window table, no resident set, no streaming, no multi-device form (follow-ups).
+// Decoding compressed bases and checking them (curve, subgroup) is msm_g2_points.inc: its outputs are what msm_bn254_g2_device takes.
 
 namespace {
 

@@ -45,6 +45,7 @@
 #include "msm_planner.hpp"
 #include "msm_kernels.hpp"
 #include "msm_kernels_g2.hpp"
+#include "msm_kernels_g2_points.hpp"
 
 namespace {
 
@@ -1997,6 +1998,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 
 #include "msm_multi.inc"
 #include "msm_g2.inc"
+#include "msm_g2_points.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS
 #include "msm_testhooks.inc"

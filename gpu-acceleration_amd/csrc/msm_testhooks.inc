@@ -93,6 +93,27 @@ int32_t msm_test_g1_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uint32_
     const bool affine_b = op == MSM_OP_G1_MADD || op == MSM_OP_G1_MADD_M256 || op == MSM_OP_G1_MADD_M256_NEG;
     return run_test_kernel(c, true, op, a, 24, op == MSM_OP_G1_DBL ? nullptr : b, affine_b ? 16 : 24, out, 24, n);
 }
+// the root-and-sign routine of k_g2_decompress (msm_kernels_g2_points.hpp g2_sqrt_signed) on arbitrary Fq2 values
+int32_t msm_test_g2_sqrt(msm_ctx* c, const uint32_t* a_std, const uint8_t* want_larger, uint32_t* out_std, uint8_t* ok, size_t n) {
+    if (!c || !a_std || !want_larger || !out_std || !ok) return MSM_ERR_BAD_ARG;
+    if (n == 0) return MSM_ERR_EMPTY;
+    if (n > 0x7FFFFFFFull) return fail(c, MSM_ERR_BAD_ARG, "n too large");
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    DevTmp ta, tw, tout, tok;  // freed on every exit path
+    HIPCHK(c, hipMalloc(&ta.p, n * 64));
+    HIPCHK(c, hipMalloc(&tw.p, n));
+    HIPCHK(c, hipMalloc(&tout.p, n * 64));
+    HIPCHK(c, hipMalloc(&tok.p, n));
+    HIPCHK(c, hipMemcpy(ta.p, a_std, n * 64, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tw.p, want_larger, n, hipMemcpyHostToDevice));
+    msmk::k_g2_test_sqrt<<<grid1(n, 256), 256, 0, c->stream>>>((const uint32_t*)ta.p, (const uint8_t*)tw.p, (uint32_t)n, (uint32_t*)tout.p, (uint8_t*)tok.p);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(out_std, tout.p, n * 64, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ok, tok.p, n, hipMemcpyDeviceToHost));
+    return MSM_OK;
+}
 int32_t msm_calibrate(msm_ctx* c, double* mad_per_s, double* fp_mul_per_s) {
     if (!c) return MSM_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -24,6 +24,7 @@ FLAG_UNSIGNED_DIGITS = 1
 FLAG_NO_GLV = 2
 FLAG_WINDOW_TABLE = 4  # resident sets carry their window table
 FLAG_DETERMINISTIC = 8  # jacobian_mont is the canonical Z = 1 representative: the same 24 words for the same group element (ABI 6)
+G2_CHECK_CURVE, G2_CHECK_SUBGROUP = 1, 2  # MSM_G2_CHECK_*: coordinates < p and on the twist / [r]P = O (implies the curve check)
 OK, ERR_EMPTY, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE, ERR_INVALID_DATA = 0, -1, -2, -3, -4, -5, -6, -7
 
 # every symbol include/msm_hip.h declares (checked by tests/test_abi.py)
@@ -37,6 +38,8 @@ ABI_SYMBOLS = [
     "msm_bn254_g1_multi", "msm_bn254_g1_multi_arkworks", "msm_bn254_g1_multi_device", "msm_multi_get_timings",
     "msm_multi_get_exchange_stats", "msm_multi_get_exchange_probe",
     "msm_bn254_g2", "msm_bn254_g2_device", "msm_bn254_g2_combine",
+    "msm_bn254_g2_compress", "msm_bn254_g2_decompress", "msm_bn254_g2_decompress_device", "msm_bn254_g2_validate", "msm_bn254_g2_validate_device",
+    "msm_bn254_g1_validate",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -143,6 +146,13 @@ def bind_product_abi(L):
     L.msm_bn254_g2.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, _u32p, _u32p, _u8p]
     L.msm_bn254_g2_device.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, _u32p, _u32p, _u8p]
     L.msm_bn254_g2_combine.argtypes = [_u32p, C.c_size_t, C.c_uint32, _u32p, _u32p, _u8p]
+    i64p = C.POINTER(C.c_int64)
+    L.msm_bn254_g2_compress.argtypes = [_u32p, C.c_uint32, _u8p, C.c_size_t, _u8p]
+    L.msm_bn254_g2_decompress.argtypes = [vp, _u8p, C.c_size_t, C.c_uint32, _u32p, _u8p, i64p]
+    L.msm_bn254_g2_decompress_device.argtypes = [vp, _u8p, C.c_size_t, C.c_uint32, vp, vp, vp, i64p]
+    L.msm_bn254_g2_validate.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_size_t, C.c_uint32, i64p]
+    L.msm_bn254_g2_validate_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, i64p]
+    L.msm_bn254_g1_validate.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_size_t, i64p]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -270,6 +280,23 @@ def compress_points(bases, form=FORM_STD, inf=None):
     return out.tobytes()
 
 
+def compress_points_g2(bases, form=FORM_STD, inf=None):
+    """Host-side inverse of MsmContext.decompress_g2: n x 32 coordinate words (x.c0, x.c1, y.c0, y.c1) -> n x 64 bytes, the images of ark-serialize 0.4
+    G2Affine::serialize_compressed (no GPU needed)."""
+    bases = _words(bases, 32)
+    if bases.shape[0] == 0:
+        raise MsmError(ERR_EMPTY, "Empty input")
+    out = np.zeros(bases.shape[0] * 64, np.uint8)
+    infp = None
+    if inf is not None:
+        inf = np.ascontiguousarray(inf, dtype=np.uint8)
+        infp = inf.ctypes.data_as(_u8p)
+    rc = load_library().msm_bn254_g2_compress(_p32(bases), form, infp, bases.shape[0], out.ctypes.data_as(_u8p))
+    if rc != 0:
+        raise MsmError(rc, "msm_bn254_g2_compress failed (%d)" % rc)
+    return out.tobytes()
+
+
 class MsmContext:
     """Persistent engine context (replaces MetalMSMPipeline, rebuilt per call in the reference)."""
 
@@ -351,13 +378,13 @@ class MsmContext:
         self._check(self._lib.msm_bn254_g1_upload_bases(self._h, _p32(bases), form, infp, bases.shape[0]))
 
     @staticmethod
-    def _images(images):
+    def _images(images, size=32):
         buf = np.frombuffer(images, dtype=np.uint8) if isinstance(images, (bytes, bytearray, memoryview)) else \
             np.ascontiguousarray(images, dtype=np.uint8).reshape(-1)
         if buf.size == 0:
             raise MsmError(ERR_EMPTY, "Empty input")
-        if buf.size % 32:
-            raise MsmError(ERR_BAD_ARG, "compressed G1Affine images are 32 bytes each")
+        if buf.size % size:
+            raise MsmError(ERR_BAD_ARG, "compressed %s images are %d bytes each" % ("G1Affine" if size == 32 else "G2Affine", size))
         return np.ascontiguousarray(buf)
 
     def decompress(self, images):
@@ -463,6 +490,59 @@ class MsmContext:
         jac, oi = np.zeros(48, np.uint32), C.c_uint8(0)
         self._check(self._lib.msm_bn254_g2_device(self._h, d_bases_ptr, d_inf_ptr, d_scalars_ptr, n, stream, _p32(jac), None, C.byref(oi)))
         return G2Result(jac, None, oi.value)  # affine words on demand (G2Result.affine_std)
+
+    # -- G2 bases from outside: compressed images, curve and subgroup checks (the square roots and [r]P = O run on the GPU) --------
+    def decompress_g2(self, images, checks=0):
+        """ark-serialize 0.4 `serialize_compressed` G2Affine images (n x 64 bytes) -> (xy Montgomery words n x 32, inf n).  checks: 0 or
+        G2_CHECK_SUBGROUP (the curve check is inherent).  An invalid image raises MsmError(ERR_INVALID_DATA) with .first_invalid set; the message
+        says "decode", "curve" or "subgroup"."""
+        buf = self._images(images, 64)
+        n = buf.size // 64
+        xy, inf, bad = np.zeros((n, 32), np.uint32), np.zeros(n, np.uint8), C.c_int64(-1)
+        rc = self._lib.msm_bn254_g2_decompress(self._h, buf.ctypes.data_as(_u8p), n, checks, _p32(xy), inf.ctypes.data_as(_u8p), C.byref(bad))
+        self._check_invalid(rc, bad)
+        return xy, inf
+
+    def decompress_g2_device(self, images, d_out_ptr, d_inf_ptr, checks=0, stream=None):
+        """the same into caller-owned device memory (raw pointers: n x 128 bytes and n bytes) -- what msm_g2_device takes; returns n"""
+        buf = self._images(images, 64)
+        n, bad = buf.size // 64, C.c_int64(-1)
+        rc = self._lib.msm_bn254_g2_decompress_device(self._h, buf.ctypes.data_as(_u8p), n, checks, d_out_ptr, d_inf_ptr, stream, C.byref(bad))
+        self._check_invalid(rc, bad)
+        return n
+
+    @staticmethod
+    def _inf_ptr(inf):
+        if inf is None:
+            return None, None
+        inf = np.ascontiguousarray(inf, dtype=np.uint8)
+        return inf, inf.ctypes.data_as(_u8p)
+
+    def validate_g2(self, bases, form=FORM_STD, inf=None, checks=G2_CHECK_SUBGROUP):
+        """n x 32 coordinate words: every component < p and the point on the twist (G2_CHECK_CURVE), in the subgroup of order r (G2_CHECK_SUBGROUP,
+        which implies the former).  Returns None; an invalid point raises MsmError(ERR_INVALID_DATA) with .first_invalid set."""
+        bases = _words(bases, 32)
+        if bases.shape[0] == 0:
+            raise MsmError(ERR_EMPTY, "Empty input")
+        inf, infp = self._inf_ptr(inf)
+        bad = C.c_int64(-1)
+        self._check_invalid(self._lib.msm_bn254_g2_validate(self._h, _p32(bases), form, infp, bases.shape[0], checks, C.byref(bad)), bad)
+
+    def validate_g2_device(self, d_bases_ptr, n, d_inf_ptr=None, checks=G2_CHECK_SUBGROUP, stream=None):
+        """the same on n x 32 Montgomery words already in HBM (raw device pointers)"""
+        if n == 0:
+            raise MsmError(ERR_EMPTY, "Empty input")
+        bad = C.c_int64(-1)
+        self._check_invalid(self._lib.msm_bn254_g2_validate_device(self._h, d_bases_ptr, d_inf_ptr, n, checks, stream, C.byref(bad)), bad)
+
+    def validate_g1(self, bases, form=FORM_STD, inf=None):
+        """n x 16 coordinate words of G1 points: coordinates < p and y^2 = x^3 + 3 (the cofactor is 1: nothing else to check)"""
+        bases = _words(bases, 16)
+        if bases.shape[0] == 0:
+            raise MsmError(ERR_EMPTY, "Empty input")
+        inf, infp = self._inf_ptr(inf)
+        bad = C.c_int64(-1)
+        self._check_invalid(self._lib.msm_bn254_g1_validate(self._h, _p32(bases), form, infp, bases.shape[0], C.byref(bad)), bad)
 
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))

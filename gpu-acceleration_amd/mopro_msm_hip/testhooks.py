@@ -18,6 +18,7 @@ HOOK_SYMBOLS = [
     "msm_bn254_g1_generate_device", "msm_bn254_generate_scalars_host", "msm_test_fp_op", "msm_test_g1_op",
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
+    "msm_test_g2_sqrt",
 ]
 _lib = None
 
@@ -40,6 +41,7 @@ def load_hooks_library():
     L.msm_bn254_generate_scalars_host.argtypes = [C.c_uint64, C.c_size_t, C.c_int, _u32p]
     L.msm_test_fp_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_g1_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
+    L.msm_test_g2_sqrt.argtypes = [vp, _u32p, _u8p, _u32p, _u8p, C.c_size_t]
     L.msm_test_decompose.argtypes = [vp, _u32p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32)]
     L.msm_test_abandon_after_sort.argtypes = [vp, _u32p, C.c_size_t]
     L.msm_calibrate.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -90,6 +92,14 @@ class HooksContext(MsmContext):
         out = np.zeros_like(a)
         self._check(self._lib.msm_test_g1_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
         return out
+
+    def test_g2_sqrt(self, a_std, want_larger):
+        """k_g2_decompress's root-and-sign routine on Fq2 values (n x 16 standard-form words): (roots n x 16 standard-form words, ok n bytes)"""
+        a = _words(a_std, 16)
+        want = np.ascontiguousarray(want_larger, dtype=np.uint8)
+        out, ok = np.zeros_like(a), np.zeros(a.shape[0], np.uint8)
+        self._check(self._lib.msm_test_g2_sqrt(self._h, _p32(a), want.ctypes.data_as(_u8p), _p32(out), ok.ctypes.data_as(_u8p), a.shape[0]))
+        return out, ok
 
     def abandon_after_sort(self, scalars):
         """decomposition + sort + piece plan of an MSM on `scalars`, then the failure a copy / event wait in front of the accumulation would be:

@@ -270,7 +270,8 @@ int32_t msm_bn254_g1_combine_flags(const uint32_t *partials_jacobian_mont, size_
  * MSM_FLAG_UNSIGNED_DIGITS and window_bits are honoured; a scalar >= 2^254 fails the call with MSM_ERR_BAD_ARG and the context stays usable;
  * msm_get_timings describes the last call.  No window table, resident set or batch form.
  * bases_xy: n x 32 words (x.c0, x.c1, y.c0, y.c1; 8 words each), MSM_FORM_STD or MSM_FORM_MONT (= the words of ark_bn254 Fq2, R = 2^256);
- *   the points are NOT validated: they must lie in G2 (what arkworks' G2Affine guarantees).
+ *   the MSM itself does NOT validate the points: they must lie in G2 (what arkworks' G2Affine guarantees).  msm_bn254_g2_decompress(_device) and
+ *   msm_bn254_g2_validate(_device) below give that guarantee on the GPU for bases that come from outside.
  * inf_mask: n bytes or NULL; scalars: n x 8 words, standard form.
  * out_jacobian_mont = X.c0 X.c1 Y.c0 Y.c1 Z.c0 Z.c1 (R = 2^256 Montgomery words; the identity is (1, 1, 0)), out_affine_std = x.c0 x.c1 y.c0 y.c1
  *   in standard form (all zero for the identity); both nullable.  Errors as for msm_bn254_g1: MSM_ERR_EMPTY for n = 0, MSM_ERR_BAD_ARG for a NULL
@@ -287,6 +288,44 @@ int32_t msm_bn254_g2_device(msm_ctx *ctx, const void *d_bases_mont, const void *
  * representative), any other bit MSM_ERR_BAD_ARG; k = 0 MSM_ERR_EMPTY. */
 int32_t msm_bn254_g2_combine(const uint32_t *partials_jacobian_mont, size_t k, uint32_t flags,
                              uint32_t out_jacobian_mont[48], uint32_t out_affine_std[32], uint8_t *out_is_inf);
+
+/* ---- getting G2 bases in safely: compressed images, curve and subgroup checks ------------------------------------------------
+ * arkworks checks every point when a key is deserialized, on the CPU: one Fq2 square root per compressed point, and one subgroup test per point --
+ * the twist's cofactor is 2p - r, not 1, so a point on the twist need not lie in G2.  Here both run on the GPU, one thread per point.
+ * Image format (what ark-serialize 0.4 writes for G2Affine::serialize_compressed): 64 bytes = x.c0 then x.c1, each 32 bytes little-endian in
+ * standard form; the two flag bits sit in the top bits of byte 63 (the same positions relative to the last coordinate as in the G1 image):
+ * bit 7 = y is the larger of (y, -y), bit 6 = the point at infinity.  Fq2 elements are ordered by c1 first, then by c0, each compared as a
+ * standard-form integer; an all-zero y counts as not larger.  (No arkworks source or Rust toolchain exists on the build machine: like the G1
+ * rule, this one rests on the documented ark-ff 0.4 ordering of quadratic extensions and ark-ec 0.4 SWFlags -- SURVEY.md Appendix C.)
+ * An image is INVALID when both flag bits are set, a component is >= p, or x^3 + 3/(9+u) is not a square; with MSM_G2_CHECK_SUBGROUP a point
+ * outside G2 is invalid too.  An invalid point fails the whole call with MSM_ERR_INVALID_DATA, *first_invalid (nullable) receives the lowest such
+ * index (-1 otherwise) and msm_last_error() says what failed: "decode" (flags, range), "curve" or "subgroup".  The context stays usable.
+ * Points flagged infinite (image bit, inf_mask) pass every check; their output coordinates are zero.  n == 0: MSM_ERR_EMPTY.
+ * The subgroup test evaluates [x+1]P + psi([x]P) + psi^2([x]P) = psi^3([2x]P) (x the BN parameter, psi the untwist-Frobenius-twist map), which on the
+ * twist is equivalent to [r]P = O.  All calls block until the verdict is on the host. */
+#define MSM_G2_CHECK_CURVE    1u  /* coordinates < p and y^2 = x^3 + 3/(9+u) */
+#define MSM_G2_CHECK_SUBGROUP 2u  /* [r]P = O; implies the curve check */
+/* host only, no context, no GPU: bases as for msm_bn254_g2 -> n x 64 bytes.  MSM_ERR_BAD_ARG for a NULL pointer or a bad form. */
+int32_t msm_bn254_g2_compress(const uint32_t *bases_xy, uint32_t base_form, const uint8_t *inf_mask,
+                              size_t n, uint8_t *out_compressed);
+/* n x 64 bytes (host) -> n x 32 arkworks Montgomery words + n infinity bytes (host).  The curve check is inherent (the root is verified):
+ * checks only adds MSM_G2_CHECK_SUBGROUP; unknown bits MSM_ERR_BAD_ARG.  Pageable caller memory is pinned in place for the copies. */
+int32_t msm_bn254_g2_decompress(msm_ctx *ctx, const uint8_t *compressed, size_t n, uint32_t checks,
+                                uint32_t *out_xy_mont, uint8_t *out_inf, int64_t *first_invalid);
+/* same, results left in caller-owned device memory (n x 128 bytes, 16-byte aligned, and n bytes): exactly what msm_bn254_g2_device takes.  The
+ * images are staged in the context's workspace; hip_stream NULL = the context's stream. */
+int32_t msm_bn254_g2_decompress_device(msm_ctx *ctx, const uint8_t *compressed, size_t n, uint32_t checks,
+                                       void *d_out_xy_mont, void *d_out_inf, void *hip_stream,
+                                       int64_t *first_invalid);
+/* uncompressed bases (e.g. a snarkjs zkey's Montgomery words): host and device forms.  checks = MSM_G2_CHECK_CURVE, MSM_G2_CHECK_SUBGROUP or
+ * both; 0 or an unknown bit: MSM_ERR_BAD_ARG.  Nothing is written but the verdict. */
+int32_t msm_bn254_g2_validate(msm_ctx *ctx, const uint32_t *bases_xy, uint32_t base_form,
+                              const uint8_t *inf_mask, size_t n, uint32_t checks, int64_t *first_invalid);
+int32_t msm_bn254_g2_validate_device(msm_ctx *ctx, const void *d_bases_mont, const void *d_inf_mask,
+                                     size_t n, uint32_t checks, void *hip_stream, int64_t *first_invalid);
+/* G1's cofactor is 1: coordinates < p and y^2 = x^3 + 3 ("curve") */
+int32_t msm_bn254_g1_validate(msm_ctx *ctx, const uint32_t *bases_xy, uint32_t base_form,
+                              const uint8_t *inf_mask, size_t n, int64_t *first_invalid);
 
 /* ---- multi-GPU inside ONE process (the reference has no multi-device code: host/gpu.rs:3-5 opens the
  *      system default device).  The caller-facing signature is the same as the single-GPU calls; the point range is cut

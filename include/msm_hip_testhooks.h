@@ -38,6 +38,11 @@ int32_t msm_test_fp_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint3
 #define MSM_OP_G1_MADD_M256 4u     /* as MADD, b's arkworks words gathered as they are (fp_unpack_shl5 + xyzz_madd_m32: k_accumulate_pieces<.., M256>) */
 #define MSM_OP_G1_MADD_M256_NEG 5u /* a - b by the same path (the digit's sign applied to S2) */
 int32_t msm_test_g1_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
+/* the root-and-sign routine of k_g2_decompress on arbitrary Fq2 values (curve points whose y has a zero component cannot be constructed in closed
+ * form: this is how the c1 = 0 / c0 = 0 branches of the sign rule get tested).  a_std: n x 16 standard-form words (c0, c1; canonical);
+ * want_larger: n bytes (non-zero: the root that is the larger of (y, -y), see msm_bn254_g2_compress); out_std: n x 16 standard-form words of the
+ * root (zero when there is none); ok: n bytes, 1 = a is a square. */
+int32_t msm_test_g2_sqrt(msm_ctx *ctx, const uint32_t *a_std, const uint8_t *want_larger, uint32_t *out_std, uint8_t *ok, size_t n);
 /* signed/unsigned digit decomposition of the planner's choice, digits[w*n + i] as int32 */
 int32_t msm_test_decompose(msm_ctx *ctx, const uint32_t *scalars, size_t n, uint32_t window_bits, int32_t *digits);
 

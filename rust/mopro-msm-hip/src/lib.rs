@@ -78,6 +78,32 @@ extern "C" {
     ) -> i32;
 }
 
+/// `checks` of the G2 decoding / validation calls (include/msm_hip.h MSM_G2_CHECK_*)
+pub const G2_CHECK_CURVE: u32 = 1;
+pub const G2_CHECK_SUBGROUP: u32 = 2;
+
+// Getting G2 bases in safely (include/msm_hip.h "getting G2 bases in safely"): what a key loader calls instead of arkworks' per-point
+// `deserialize_compressed` / `check()` on the CPU -- see INTEGRATION.md.  Declarations only: the shim's G2 surface is the C ABI itself.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_g2_compress(bases_xy: *const u32, base_form: u32, inf_mask: *const u8, n: usize, out_compressed: *mut u8) -> i32;
+    pub fn msm_bn254_g2_decompress(
+        ctx: *mut MsmCtx, compressed: *const u8, n: usize, checks: u32, out_xy_mont: *mut u32, out_inf: *mut u8, first_invalid: *mut i64,
+    ) -> i32;
+    pub fn msm_bn254_g2_decompress_device(
+        ctx: *mut MsmCtx, compressed: *const u8, n: usize, checks: u32, d_out_xy_mont: *mut core::ffi::c_void, d_out_inf: *mut core::ffi::c_void,
+        hip_stream: *mut core::ffi::c_void, first_invalid: *mut i64,
+    ) -> i32;
+    pub fn msm_bn254_g2_validate(
+        ctx: *mut MsmCtx, bases_xy: *const u32, base_form: u32, inf_mask: *const u8, n: usize, checks: u32, first_invalid: *mut i64,
+    ) -> i32;
+    pub fn msm_bn254_g2_validate_device(
+        ctx: *mut MsmCtx, d_bases_mont: *const core::ffi::c_void, d_inf_mask: *const core::ffi::c_void, n: usize, checks: u32,
+        hip_stream: *mut core::ffi::c_void, first_invalid: *mut i64,
+    ) -> i32;
+    pub fn msm_bn254_g1_validate(ctx: *mut MsmCtx, bases_xy: *const u32, base_form: u32, inf_mask: *const u8, n: usize, first_invalid: *mut i64) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 

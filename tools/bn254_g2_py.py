@@ -186,6 +186,89 @@ def chain_points(a, d, m, block=512):
     return pts[:m]
 
 
+# ---- Fq2 powers and square roots, the Frobenius endomorphism, the subgroup test, compressed images ----------------------------------
+def pow2(a, e):
+    r, b = (1, 0), a
+    while e:
+        if e & 1:
+            r = mul2(r, b)
+        b = mul2(b, b)
+        e >>= 1
+    return r
+
+
+def sqrt2(a):
+    """a square root of a in Fq2 (p = 3 mod 4, the two-exponentiation "complex" method), or None when a is not a square"""
+    a1 = pow2(a, (P - 3) // 4)
+    alpha = mul2(mul2(a1, a1), a)
+    x0 = mul2(a1, a)
+    if alpha == (P - 1, 0):
+        x = mul2((0, 1), x0)
+    else:
+        x = mul2(pow2(add2((1, 0), alpha), (P - 1) // 2), x0)
+    return x if mul2(x, x) == a else None
+
+
+def is_larger2(y):
+    """y > -y in the order of ark-ff 0.4's quadratic extensions: c1 first, then c0, each as a standard-form integer (0 is not larger)"""
+    n = neg2(y)
+    return (y[1], y[0]) > (n[1], n[0])
+
+
+XI = (9, 1)
+PSI_X = pow2(XI, (P - 1) // 3)
+PSI_Y = pow2(XI, (P - 1) // 2)
+COFACTOR = 2 * P - R  # of the twist: #E'(Fq2) = r * (2p - r)
+
+
+def conj2(a):
+    return (a[0], (-a[1]) % P)
+
+
+def psi(pt):
+    """the untwist-Frobenius-twist endomorphism: (conj(x) * xi^((p-1)/3), conj(y) * xi^((p-1)/2)); acts on G2 as multiplication by p"""
+    if pt is None:
+        return None
+    return (mul2(conj2(pt[0]), PSI_X), mul2(conj2(pt[1]), PSI_Y))
+
+
+def in_subgroup(pt):
+    """the DEFINING test [r]P = O (pt on the twist)"""
+    return mul_raw(pt, R) is None
+
+
+def compress(pt):
+    """64-byte image of ark-serialize 0.4 G2Affine::serialize_compressed: x.c0, x.c1 (32 bytes each, little-endian, standard form);
+    byte 63 bit 7 = y is the larger of (y, -y), bit 6 = infinity"""
+    if pt is None:
+        return bytes(63) + bytes([0x40])
+    b = bytearray(pt[0][0].to_bytes(32, "little") + pt[0][1].to_bytes(32, "little"))
+    if is_larger2(pt[1]):
+        b[63] |= 0x80
+    return bytes(b)
+
+
+def decompress(img):
+    """image -> (point or None for infinity); raises ValueError("decode" / "curve") for an invalid image.  No subgroup test."""
+    assert len(img) == 64
+    larger, inf = img[63] >> 7, (img[63] >> 6) & 1
+    if larger and inf:
+        raise ValueError("decode")
+    x0 = int.from_bytes(img[:32], "little")
+    x1 = int.from_bytes(img[32:63] + bytes([img[63] & 0x3F]), "little")
+    if x0 >= P or x1 >= P:
+        raise ValueError("decode")
+    if inf:
+        return None
+    x = (x0, x1)
+    y = sqrt2(add2(mul2(mul2(x, x), x), B_TWIST))
+    if y is None:
+        raise ValueError("curve")
+    if bool(larger) != is_larger2(y):
+        y = neg2(y)
+    return (x, y)
+
+
 def glv_lambda_beta():
     """(lambda, beta): the nontrivial cube roots of unity mod r and mod p with lambda * (x, y) = (beta * x, y) on G1 (recomputed, not imported
     from the product; the G1 side is tools/bn254_py.py)"""

@@ -83,7 +83,37 @@ int main() {
     failures += finishcheck::check_chain<HostG2>(G, "G2") + finishcheck::check_combine<HostG2>(G, "G2");
     Fq2 x, y;
     CHECK(to_affine_std(identity(), x, y) && is_zero(x) && is_zero(y), "identity -> (0, 0)");
+    // compress_point (msm_bn254_g2_compress): x bytes, the infinity bit, and the order of y -- c1 first, then c0; 0 is not larger
+    {
+        uint32_t w[32], ws[32];
+        store_words(w, G.x), store_words(w + 16, G.y);
+        store_words(ws, from_mont(G.x)), store_words(ws + 16, from_mont(G.y));
+        uint8_t im[64], is_[64], in_[64], inf[64];
+        compress_point(w, true, false, im);
+        compress_point(ws, false, false, is_);
+        CHECK(std::memcmp(im, is_, 64) == 0 && std::memcmp(im, ws, 63) == 0, "compress: both forms agree, x in standard form");
+        CHECK((im[63] & 0x40) == 0, "compress: no infinity bit");
+        store_words(w + 16, sub(zero(), G.y));
+        compress_point(w, true, false, in_);
+        CHECK(std::memcmp(im, in_, 63) == 0 && ((im[63] ^ in_[63]) == 0x80), "compress: y and -y differ in bit 7 alone");
+        compress_point(w, true, true, inf);
+        bool zeros = inf[63] == 0x40;
+        for (int i = 0; i < 63; i++) zeros = zeros && inf[i] == 0;
+        CHECK(zeros, "compress: infinity");
+        auto larger = [&](uint64_t c0, uint64_t c1, bool neg0, bool neg1) {
+            Fq a{{c0, 0, 0, 0}}, b{{c1, 0, 0, 0}};
+            if (neg0) a = hostg1::sub(Fq{{0, 0, 0, 0}}, hostg1::to_mont(a)), a = hostg1::from_mont(a);
+            if (neg1) b = hostg1::sub(Fq{{0, 0, 0, 0}}, hostg1::to_mont(b)), b = hostg1::from_mont(b);
+            uint32_t v[32] = {};
+            hostg1::store_words(v + 16, a), hostg1::store_words(v + 24, b);
+            uint8_t o[64];
+            compress_point(v, false, false, o);
+            return (o[63] & 0x80) != 0;
+        };
+        CHECK(!larger(0, 0, false, false) && !larger(1, 0, false, false) && larger(1, 0, true, false), "compress: c1 = 0, c0 decides");
+        CHECK(!larger(1, 1, true, false) && larger(1, 1, false, true) && !larger(0, 1, false, false) && larger(0, 1, false, true), "compress: c1 decides");
+    }
     if (failures) return 1;
-    std::printf("host_g2.hpp: folds, Horner chain, combine outputs, affine conversion -- clean under ASan/UBSan\n");
+    std::printf("host_g2.hpp: folds, Horner chain, combine outputs, affine conversion, compressed images -- clean under ASan/UBSan\n");
     return 0;
 }
