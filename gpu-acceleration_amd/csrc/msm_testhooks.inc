@@ -421,4 +421,15 @@ int32_t msm_test_abandon_after_sort(msm_ctx* c, const uint32_t* scalars, size_t 
     return fail(c, MSM_ERR_HIP, "test hook: the call was abandoned between its sort and its accumulation");
 }
 
+int32_t msm_test_ntt_set_tile_log2(msm_ctx* c, uint32_t tile_log2) {
+    if (!c) return MSM_ERR_BAD_ARG;
+    if (tile_log2 != 0 && tile_log2 != nttk::NTT_TILE_SMALL_LOG2 && tile_log2 != nttk::NTT_TILE_LOG2)
+        return fail(c, MSM_ERR_BAD_ARG, "tile_log2 = %u: 0, %u or %u", tile_log2, nttk::NTT_TILE_SMALL_LOG2, nttk::NTT_TILE_LOG2);
+    std::lock_guard<std::mutex> lk(c->mu);
+    int32_t rc = ntt_state(c);
+    if (rc) return rc;
+    c->ntt->forced_tile = tile_log2;
+    return MSM_OK;
+}
+
 }  // extern "C"

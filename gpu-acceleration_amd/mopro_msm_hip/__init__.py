@@ -24,6 +24,7 @@ FLAG_UNSIGNED_DIGITS = 1
 FLAG_NO_GLV = 2
 FLAG_WINDOW_TABLE = 4  # resident sets carry their window table
 FLAG_DETERMINISTIC = 8  # jacobian_mont is the canonical Z = 1 representative: the same 24 words for the same group element (ABI 6)
+NTT_INVERSE, NTT_IN_MONT, NTT_OUT_MONT = 1, 2, 4  # MSM_NTT_*: inverse transform (1/n included) / input words are arkworks Fr.0 / output words likewise
 G2_CHECK_CURVE, G2_CHECK_SUBGROUP = 1, 2  # MSM_G2_CHECK_*: coordinates < p and on the twist / [r]P = O (implies the curve check)
 OK, ERR_EMPTY, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE, ERR_INVALID_DATA = 0, -1, -2, -3, -4, -5, -6, -7
 
@@ -40,6 +41,7 @@ ABI_SYMBOLS = [
     "msm_bn254_g2", "msm_bn254_g2_device", "msm_bn254_g2_combine",
     "msm_bn254_g2_compress", "msm_bn254_g2_decompress", "msm_bn254_g2_decompress_device", "msm_bn254_g2_validate", "msm_bn254_g2_validate_device",
     "msm_bn254_g1_validate",
+    "msm_bn254_fr_root_of_unity", "msm_bn254_fr_ntt_plan", "msm_bn254_fr_ntt_device", "msm_bn254_fr_ntt", "msm_bn254_fr_mul_sub_scale_device",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -153,6 +155,11 @@ def bind_product_abi(L):
     L.msm_bn254_g2_validate.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_size_t, C.c_uint32, i64p]
     L.msm_bn254_g2_validate_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, i64p]
     L.msm_bn254_g1_validate.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_size_t, i64p]
+    L.msm_bn254_fr_root_of_unity.argtypes = [C.c_uint32, _u32p]
+    L.msm_bn254_fr_ntt_plan.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), _u32p]
+    L.msm_bn254_fr_ntt_device.argtypes = [vp, vp, C.c_uint32, C.c_size_t, C.c_uint32, _u32p, vp]
+    L.msm_bn254_fr_ntt.argtypes = [vp, _u32p, _u32p, C.c_uint32, C.c_size_t, C.c_uint32, _u32p]
+    L.msm_bn254_fr_mul_sub_scale_device.argtypes = [vp, vp, vp, vp, _u32p, vp, C.c_size_t, C.c_uint32, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -249,6 +256,35 @@ def plan(n, window_bits=0, flags=0, _lib=None):
     if rc != OK:
         raise MsmError(rc, "Empty input" if rc == ERR_EMPTY else f"msm_plan failed ({rc})")
     return p
+
+
+def _fr_words(v):
+    """a scalar-field element for the C ABI: None stays None, an int becomes its 8 little-endian words, words pass through"""
+    if v is None:
+        return None
+    if isinstance(v, int):
+        if not 0 <= v < 1 << 256:
+            raise MsmError(ERR_BAD_ARG, "a field element is 256 bits")
+        return np.array([(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)], np.uint32)
+    return np.ascontiguousarray(v, dtype=np.uint32).reshape(8)
+
+
+def fr_root_of_unity(log_n):
+    """the primitive 2^log_n-th root of unity the transforms use, as an int (arkworks' / snarkjs' root; host only)"""
+    out = np.zeros(8, np.uint32)
+    rc = load_library().msm_bn254_fr_root_of_unity(log_n, _p32(out))
+    if rc != OK:
+        raise MsmError(rc, "log_n = %d: r - 1 has 28 factors of two" % log_n)
+    return sum(int(w) << (32 * i) for i, w in enumerate(out.tolist()))
+
+
+def ntt_plan(log_n):
+    """the widths (bits) of the passes a transform of 2^log_n elements makes over global memory (host only)"""
+    passes, radix = C.c_uint32(0), np.zeros(8, np.uint32)
+    rc = load_library().msm_bn254_fr_ntt_plan(log_n, C.byref(passes), _p32(radix))
+    if rc != OK:
+        raise MsmError(rc, "log_n = %d: r - 1 has 28 factors of two" % log_n)
+    return [int(t) for t in radix[:passes.value]]
 
 
 def combine_partials(partials_jacobian_mont, want_affine=True, flags=0):
@@ -543,6 +579,34 @@ class MsmContext:
         inf, infp = self._inf_ptr(inf)
         bad = C.c_int64(-1)
         self._check_invalid(self._lib.msm_bn254_g1_validate(self._h, _p32(bases), form, infp, bases.shape[0], C.byref(bad)), bad)
+
+    # -- BN254 scalar field: transforms in HBM (the H scalars of a Groth16 proof) ---------------------
+    def ntt(self, values, log_n, batch=1, flags=0, coset=None, out=None):
+        """host arrays: batch x 2^log_n elements of 8 words, natural order in and out; flags NTT_*; coset: generator g (int or 8 words,
+        standard form) or None.  Returns the (batch * n) x 8 result: a new array, or `out` (a contiguous uint32 array, which may be `values`
+        itself: the call then works in place)."""
+        a = _words(values, 8)
+        if a.shape[0] == 0 or batch == 0:
+            raise MsmError(ERR_EMPTY, "Empty input")
+        if 0 <= log_n <= 28 and a.shape[0] != batch << log_n:
+            raise MsmError(ERR_BAD_ARG, "%d elements given, batch x 2^log_n = %d" % (a.shape[0], batch << log_n))
+        if out is None:
+            out = np.zeros_like(a)
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.flags.c_contiguous and out.size == a.size):
+                raise MsmError(ERR_BAD_ARG, "out must be a contiguous uint32 array of the input's size")
+            out = out.reshape(-1, 8)
+        g = _fr_words(coset)
+        self._check(self._lib.msm_bn254_fr_ntt(self._h, _p32(a), _p32(out), log_n, batch, flags, _p32(g)))
+        return out
+
+    def ntt_device(self, d_ptr, log_n, batch=1, flags=0, coset=None, stream=None):
+        """in place on batch x 2^log_n elements already in HBM (raw device pointer); enqueued on `stream` (None: the context's)"""
+        self._check(self._lib.msm_bn254_fr_ntt_device(self._h, d_ptr, log_n, batch, flags, _p32(_fr_words(coset)), stream))
+
+    def fr_mul_sub_scale_device(self, d_a, d_b, d_c, d_out, n, k=None, flags=0, stream=None):
+        """out[i] = (a[i] * b[i] - c[i]) * k on raw device pointers; d_c None: no subtrahend; k None: 1; d_out may alias an input"""
+        self._check(self._lib.msm_bn254_fr_mul_sub_scale_device(self._h, d_a, d_b, d_c, _p32(_fr_words(k)), d_out, n, flags, stream))
 
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))

@@ -18,7 +18,7 @@ HOOK_SYMBOLS = [
     "msm_bn254_g1_generate_device", "msm_bn254_generate_scalars_host", "msm_test_fp_op", "msm_test_g1_op",
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
-    "msm_test_g2_sqrt",
+    "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2",
 ]
 _lib = None
 
@@ -49,6 +49,7 @@ def load_hooks_library():
     L.msm_probe_launch_chain.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     L.msm_probe_empty_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     L.msm_test_get_list_counts.argtypes = [vp, _u32p]
+    L.msm_test_ntt_set_tile_log2.argtypes = [vp, C.c_uint32]
     L.msm_probe_reduce_bits.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     L.msm_test_stage_dump.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, _u32p, _u32p, _u32p, _u32p, _u32p,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _u32p]
@@ -100,6 +101,10 @@ class HooksContext(MsmContext):
         out, ok = np.zeros_like(a), np.zeros(a.shape[0], np.uint8)
         self._check(self._lib.msm_test_g2_sqrt(self._h, _p32(a), want.ctypes.data_as(_u8p), _p32(out), ok.ctypes.data_as(_u8p), a.shape[0]))
         return out, ok
+
+    def ntt_set_tile_log2(self, tile_log2):
+        """the LDS tile (log2 elements) of the transforms that follow on this context: 4 or 10; 0 = the plan's own"""
+        self._check(self._lib.msm_test_ntt_set_tile_log2(self._h, tile_log2))
 
     def abandon_after_sort(self, scalars):
         """decomposition + sort + piece plan of an MSM on `scalars`, then the failure a copy / event wait in front of the accumulation would be:

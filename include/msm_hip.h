@@ -381,6 +381,38 @@ int32_t msm_multi_set_kernel_timing(msm_multi *m, uint32_t every_n); /* ABI 7: m
 /* msm_get_clock_stats of rank `rank`'s context (ABI 7): a slow rank of a multi-GPU call can be told from a slow CLOCK on its device */
 int32_t msm_multi_get_clock_stats(msm_multi *m, int32_t rank, double *sclk_ghz, double *cycles_per_addition, uint64_t *samples);
 
+/* ---- BN254 scalar field Fr: number-theoretic transforms in HBM (the H scalars of a Groth16 proof, made where the MSM reads them).
+ *      Elements are 8 little-endian 32-bit words, as the scalars of the MSM calls.  Added under ABI 7, as the G2 calls were.
+ *      Root: w_28 = 5^((r-1)/2^28) mod r = 19103219067921713944291392827692070036145651957329286315305642004821462161904 (arkworks'
+ *      Fr::TWO_ADIC_ROOT_OF_UNITY, snarkjs' root), w_k = w_28^(2^(28-k)).  halo2's 7-based root differs from k = 5 on and is NOT offered.
+ *      Forward:  A[j] = sum_i a[i] (g w^j)^i, g = 1 without a coset.  Inverse: the exact inverse of that, 1/n included, times g^-i after the
+ *      transform when a coset is given.  The generator is an ARGUMENT: arkworks' coset_fft uses g = 5, snarkjs' odd coset g = w_(k+1).
+ *      Any 256-bit input pattern is read modulo r; outputs are canonical (< r): results are bit-exact.  log_n == 0 converts the form only.
+ *      Errors: log_n > 28, an unknown flag bit, a NULL pointer, g = 0 (mod r), an array not aligned to 16 bytes: MSM_ERR_BAD_ARG; batch == 0
+ *      (n == 0): MSM_ERR_EMPTY; allocation failure: MSM_ERR_OOM.  The context stays usable after any of them. ---------------------------- */
+#define MSM_NTT_INVERSE  1u  /* inverse transform, 1/n included */
+#define MSM_NTT_IN_MONT  2u  /* input words are arkworks Fr.0 (x*2^256 mod r); default: standard form */
+#define MSM_NTT_OUT_MONT 4u  /* output words likewise; default: standard form = what the MSM calls take as scalars */
+/* host only, no context: the primitive 2^log_n-th root the transforms use, standard form */
+int32_t msm_bn254_fr_root_of_unity(uint32_t log_n, uint32_t out_std[8]);
+/* host only: how a transform of this size is cut into passes over global memory (radix_log2[i] bits in pass i; the array is read and written
+ * once per pass, and there is no separate reordering pass) */
+int32_t msm_bn254_fr_ntt_plan(uint32_t log_n, uint32_t *passes, uint32_t radix_log2[8]);
+/* in place on `batch` contiguous arrays of n = 2^log_n elements in device memory, natural order in AND out.
+ * coset_gen_std: NULL, or a HOST pointer to 8 words g != 0 (standard form).
+ * Stream-ordered on hip_stream (NULL = the context's stream): returns when enqueued.  The first use of a size (or of a generator) on a context
+ * builds its tables on the same stream first.  A context's calls share one scratch array: a call on another stream than the one before it
+ * waits for that one. */
+int32_t msm_bn254_fr_ntt_device(msm_ctx *ctx, void *d_data, uint32_t log_n, size_t batch, uint32_t flags,
+                                const uint32_t *coset_gen_std, void *hip_stream);
+/* host pointers, blocking; out == in allowed; pageable memory is pinned in place like every host-pointer call */
+int32_t msm_bn254_fr_ntt(msm_ctx *ctx, const uint32_t *in, uint32_t *out, uint32_t log_n, size_t batch, uint32_t flags,
+                         const uint32_t *coset_gen_std);
+/* out[i] = (a[i]*b[i] - c[i]) * k.  d_c NULL = no subtrahend.  k_std (host, 8 words) NULL = 1.  d_out may alias any input.
+ * flags: MSM_NTT_IN_MONT / MSM_NTT_OUT_MONT only.  Stream-ordered like the transform. */
+int32_t msm_bn254_fr_mul_sub_scale_device(msm_ctx *ctx, const void *d_a, const void *d_b, const void *d_c,
+                                          const uint32_t *k_std, void *d_out, size_t n, uint32_t flags, void *hip_stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 /* the plan of a call on n points under (window_bits, flags); with MSM_FLAG_WINDOW_TABLE in flags: the plan of a RESIDENT call on a
  * set of n bases uploaded under those flags (window width, table factor, table memory) */

@@ -106,6 +106,9 @@ int32_t msm_probe_reduce_bits(msm_ctx *ctx, uint32_t parts, uint32_t launches, d
 /* the list counters the last sort chain / accumulation left on the device: out[0] long-list entries, out[1] mid-list entries (buckets of 3 .. 7
  * pieces k_combine_pieces folds), out[2] pieces, out[3] partial-sum slots, out[4] buckets of exactly two pieces (listed apart) */
 int32_t msm_test_get_list_counts(msm_ctx *ctx, uint32_t out[5]);
+/* the tile size (log2 of the elements a workgroup holds in LDS) of the transforms that follow on this context: 4 or 10, the two sizes the
+ * kernels are instantiated for; 0 = back to the plan of msm_bn254_fr_ntt_plan.  With 4, 2^12 elements are a three-pass transform. */
+int32_t msm_test_ntt_set_tile_log2(msm_ctx *ctx, uint32_t tile_log2);
 
 #ifdef __cplusplus
 }

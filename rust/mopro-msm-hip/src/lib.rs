@@ -104,6 +104,30 @@ extern "C" {
     pub fn msm_bn254_g1_validate(ctx: *mut MsmCtx, bases_xy: *const u32, base_form: u32, inf_mask: *const u8, n: usize, first_invalid: *mut i64) -> i32;
 }
 
+/// `flags` of the scalar-field transforms (include/msm_hip.h MSM_NTT_*)
+pub const NTT_INVERSE: u32 = 1;
+pub const NTT_IN_MONT: u32 = 2;
+pub const NTT_OUT_MONT: u32 = 4;
+
+// The H scalars of a Groth16 proof made in HBM (include/msm_hip.h "BN254 scalar field Fr"): transforms over Fr and the
+// pointwise step between them, in front of msm_bn254_g1_resident_device.  Declarations only, like the G2 loaders above.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_fr_root_of_unity(log_n: u32, out_std: *mut u32) -> i32;
+    pub fn msm_bn254_fr_ntt_plan(log_n: u32, passes: *mut u32, radix_log2: *mut u32) -> i32;
+    pub fn msm_bn254_fr_ntt_device(
+        ctx: *mut MsmCtx, d_data: *mut core::ffi::c_void, log_n: u32, batch: usize, flags: u32, coset_gen_std: *const u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_ntt(
+        ctx: *mut MsmCtx, input: *const u32, out: *mut u32, log_n: u32, batch: usize, flags: u32, coset_gen_std: *const u32,
+    ) -> i32;
+    pub fn msm_bn254_fr_mul_sub_scale_device(
+        ctx: *mut MsmCtx, d_a: *const core::ffi::c_void, d_b: *const core::ffi::c_void, d_c: *const core::ffi::c_void, k_std: *const u32,
+        d_out: *mut core::ffi::c_void, n: usize, flags: u32, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 
