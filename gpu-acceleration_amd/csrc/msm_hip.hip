@@ -46,6 +46,7 @@
 #include "msm_kernels_g2.hpp"
 #include "msm_kernels_g2_points.hpp"
 #include "ntt_bn254.hpp"
+#include "r1cs_bn254.hpp"
 
 namespace {
 
@@ -167,6 +168,7 @@ struct Knobs {
 // half-size chunks a ragged instance ends on); three cost one more chunk of HBM.
 constexpr int STREAM_SLOTS = 3;
 struct NttState;  // msm_ntt.inc
+struct R1csState;  // msm_r1cs.inc
 struct msm_ctx {
     std::mutex mu;
     Knobs knobs;
@@ -226,11 +228,13 @@ struct msm_ctx {
     uint32_t last_sort_path = 0;  // 2 = two-level LDS sort, 1 = tiled LDS histogram, 0 = global atomics (stage tests, trace)
     bool no_host_pin = false;     // a context of an msm_multi handle: the handle pins the caller's arrays once for all its ranks (HostPin)
     NttState* ntt = nullptr;      // tables and scratch of the scalar-field transforms, made by the first of them (msm_ntt.inc)
+    R1csState* r1cs = nullptr;    // the resident constraint matrices and their scratch, made by the first upload (msm_r1cs.inc)
 };
 
 namespace {
 
 void ntt_release(msm_ctx* c);  // msm_ntt.inc
+void r1cs_release(msm_ctx* c);  // msm_r1cs.inc
 
 int32_t fail(msm_ctx* c, int32_t code, const char* fmt, ...) {
     char buf[512];
@@ -1556,6 +1560,7 @@ void msm_ctx_destroy(msm_ctx* c) {
         if (c->stream) (void)hipStreamSynchronize(c->stream);
         if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
         ntt_release(c);
+        r1cs_release(c);
         DevBuf* bufs[] = {&c->bases,   &c->inf,       &c->scalars, &c->digits,  &c->ranks,  &c->sorted, &c->hist,
                           &c->offsets, &c->blocksums, &c->buckets, &c->rc,      &c->flags,  &c->pow2,
                           &c->sorttmp, &c->tilecounts, &c->ibases, &c->longlist, &c->longdone, &c->midlist, &c->ccounts, &c->cregion, &c->bigslot, &c->big,
@@ -2076,6 +2081,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 #include "msm_g2.inc"
 #include "msm_g2_points.inc"
 #include "msm_ntt.inc"
+#include "msm_r1cs.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS
 #include "msm_testhooks.inc"

@@ -25,6 +25,8 @@ FLAG_NO_GLV = 2
 FLAG_WINDOW_TABLE = 4  # resident sets carry their window table
 FLAG_DETERMINISTIC = 8  # jacobian_mont is the canonical Z = 1 representative: the same 24 words for the same group element (ABI 6)
 NTT_INVERSE, NTT_IN_MONT, NTT_OUT_MONT = 1, 2, 4  # MSM_NTT_*: inverse transform (1/n included) / input words are arkworks Fr.0 / output words likewise
+R1CS_COEF_STD, R1CS_COEF_MONT, R1CS_COEF_MONT2 = 0, 1, 2  # MSM_R1CS_COEF_*: a coefficient's words are c / c * 2^256 (arkworks Fr.0) / c * 2^512 (a snarkjs zkey's section 4)
+R1CS_C_FROM_AB = 8  # MSM_R1CS_C_FROM_AB: the eval writes c[i] = a[i] * b[i] instead of (matrix 2) * w
 G2_CHECK_CURVE, G2_CHECK_SUBGROUP = 1, 2  # MSM_G2_CHECK_*: coordinates < p and on the twist / [r]P = O (implies the curve check)
 OK, ERR_EMPTY, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE, ERR_INVALID_DATA = 0, -1, -2, -3, -4, -5, -6, -7
 
@@ -42,6 +44,7 @@ ABI_SYMBOLS = [
     "msm_bn254_g2_compress", "msm_bn254_g2_decompress", "msm_bn254_g2_decompress_device", "msm_bn254_g2_validate", "msm_bn254_g2_validate_device",
     "msm_bn254_g1_validate",
     "msm_bn254_fr_root_of_unity", "msm_bn254_fr_ntt_plan", "msm_bn254_fr_ntt_device", "msm_bn254_fr_ntt", "msm_bn254_fr_mul_sub_scale_device",
+    "msm_bn254_fr_r1cs_plan", "msm_bn254_fr_r1cs_upload", "msm_bn254_fr_r1cs_info", "msm_bn254_fr_r1cs_eval_device", "msm_bn254_fr_r1cs_eval",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -80,6 +83,20 @@ class Timings(C.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+
+class R1csInfo(C.Structure):
+    """msm_r1cs_info_t: what an upload of constraint matrices builds"""
+    _fields_ = [("entries", C.c_uint64 * 3), ("rows_with_entries", C.c_uint64 * 3), ("longest_row", C.c_uint64), ("plus_one", C.c_uint64),
+                ("minus_one", C.c_uint64), ("distinct_values", C.c_uint64), ("work_items", C.c_uint64), ("max_item_len", C.c_uint64),
+                ("fold_rows", C.c_uint64), ("partial_sums", C.c_uint64), ("device_bytes", C.c_uint64), ("build_ms", C.c_double),
+                ("upload_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("entries", "rows_with_entries") else getattr(self, k)) for k, _ in self._fields_}
+
+
+# msm_r1cs_coef_t: matrix, row, col, 8 value words -- 44 bytes, the layout of one entry of a zkey's coefficient section
+R1CS_COEF_DTYPE = np.dtype([("matrix", "<u4"), ("row", "<u4"), ("col", "<u4"), ("value", "<u4", (8,))])
 
 _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
@@ -160,6 +177,11 @@ def bind_product_abi(L):
     L.msm_bn254_fr_ntt_device.argtypes = [vp, vp, C.c_uint32, C.c_size_t, C.c_uint32, _u32p, vp]
     L.msm_bn254_fr_ntt.argtypes = [vp, _u32p, _u32p, C.c_uint32, C.c_size_t, C.c_uint32, _u32p]
     L.msm_bn254_fr_mul_sub_scale_device.argtypes = [vp, vp, vp, vp, _u32p, vp, C.c_size_t, C.c_uint32, vp]
+    L.msm_bn254_fr_r1cs_plan.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(R1csInfo)]
+    L.msm_bn254_fr_r1cs_upload.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.msm_bn254_fr_r1cs_info.argtypes = [vp, C.POINTER(R1csInfo)]
+    L.msm_bn254_fr_r1cs_eval_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp]
+    L.msm_bn254_fr_r1cs_eval.argtypes = [vp, _u32p, C.c_size_t, _u32p, C.c_uint32]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -285,6 +307,32 @@ def ntt_plan(log_n):
     if rc != OK:
         raise MsmError(rc, "log_n = %d: r - 1 has 28 factors of two" % log_n)
     return [int(t) for t in radix[:passes.value]]
+
+
+def r1cs_coefs(coefs):
+    """constraint-matrix entries for the C ABI: a R1CS_COEF_DTYPE array passes through; bytes (a zkey's coefficient section after its count) are
+    viewed as records; an iterable of (matrix, row, col, value) with value an int < 2^256 or 8 words is packed"""
+    if isinstance(coefs, np.ndarray) and coefs.dtype == R1CS_COEF_DTYPE:
+        return np.ascontiguousarray(coefs)
+    if isinstance(coefs, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(coefs), R1CS_COEF_DTYPE).copy()
+    coefs = list(coefs)
+    out = np.zeros(len(coefs), R1CS_COEF_DTYPE)
+    for i, (m, r, c, v) in enumerate(coefs):
+        out[i] = (m, r, c, _fr_words(v))
+    return out
+
+
+def r1cs_plan(coefs, num_rows, num_cols, log_n):
+    """what MsmContext.r1cs_upload would build from these entries (host only: no context, no GPU), as a dict of msm_r1cs_info_t; the same
+    validation, with the coefficient values taken as R1CS_COEF_STD"""
+    a = r1cs_coefs(coefs)
+    info = R1csInfo()
+    lib = load_library()
+    rc = lib.msm_bn254_fr_r1cs_plan(a.ctypes.data, a.shape[0], num_rows, num_cols, log_n, C.byref(info))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_fr_r1cs_plan failed ({rc})")
+    return info.as_dict()
 
 
 def combine_partials(partials_jacobian_mont, want_affine=True, flags=0):
@@ -607,6 +655,31 @@ class MsmContext:
     def fr_mul_sub_scale_device(self, d_a, d_b, d_c, d_out, n, k=None, flags=0, stream=None):
         """out[i] = (a[i] * b[i] - c[i]) * k on raw device pointers; d_c None: no subtrahend; k None: 1; d_out may alias an input"""
         self._check(self._lib.msm_bn254_fr_mul_sub_scale_device(self._h, d_a, d_b, d_c, _p32(_fr_words(k)), d_out, n, flags, stream))
+
+    # -- BN254 scalar field: rows of the constraint matrices times the witness ([a | b | c] made in HBM) ---
+    def r1cs_upload(self, coefs, num_rows, num_cols, log_n, coef_form=R1CS_COEF_STD):
+        """make up to three constraint matrices (matrix 0, 1, 2 = A, B, C; num_rows x num_cols) resident, replacing earlier ones; the evals are
+        laid out over 2^log_n >= num_rows rows.  coefs: see r1cs_coefs.  Returns what was built (msm_r1cs_info_t as a dict)."""
+        a = r1cs_coefs(coefs)
+        self._check(self._lib.msm_bn254_fr_r1cs_upload(self._h, a.ctypes.data, a.shape[0], coef_form, num_rows, num_cols, log_n))
+        return self.r1cs_info()
+
+    def r1cs_info(self):
+        info = R1csInfo()
+        self._check(self._lib.msm_bn254_fr_r1cs_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def r1cs_eval_device(self, d_witness, n_witness, d_out, flags=0, stream=None):
+        """raw device pointers: n_witness x 8 witness words in, 3 x 2^log_n x 8 words [a | b | c] out; flags NTT_IN_MONT / NTT_OUT_MONT /
+        R1CS_C_FROM_AB; enqueued on `stream` (None: the context's)"""
+        self._check(self._lib.msm_bn254_fr_r1cs_eval_device(self._h, d_witness, n_witness, d_out, flags, stream))
+
+    def r1cs_eval(self, witness, log_n, flags=0):
+        """host arrays: the witness (num_cols x 8 words) -> the (3 * 2^log_n) x 8 words [a | b | c]; log_n as uploaded"""
+        w = _words(witness, 8)
+        out = np.zeros((3 << log_n, 8), np.uint32)
+        self._check(self._lib.msm_bn254_fr_r1cs_eval(self._h, _p32(w), w.shape[0], _p32(out), flags))
+        return out
 
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))

@@ -413,6 +413,58 @@ int32_t msm_bn254_fr_ntt(msm_ctx *ctx, const uint32_t *in, uint32_t *out, uint32
 int32_t msm_bn254_fr_mul_sub_scale_device(msm_ctx *ctx, const void *d_a, const void *d_b, const void *d_c,
                                           const uint32_t *k_std, void *d_out, size_t n, uint32_t flags, void *hip_stream);
 
+/* ---- BN254 scalar field Fr: rows of R1CS constraint matrices times the witness, in HBM (where the evaluations [a | b | c] the H recipes start
+ *      from come from: a = A w, b = B w, c = C w or c = a o b).  The matrices stay resident with the key, as the bases do; the witness is the
+ *      scalar vector of the A, B1, B2 and L query MSMs and is in HBM already.  Added under ABI 7, as the transforms were.
+ *      A record has the layout of one entry of a snarkjs zkey's coefficient section (section 4): matrix, constraint, signal, 32 little-endian
+ *      bytes -- the section's payload after its count can be handed over as it is, with MSM_R1CS_COEF_MONT2.  Any 256-bit value pattern is read
+ *      modulo r; entries may come in any order; repeated (matrix, row, col) entries add up (each counts as an entry of its row). ---------------- */
+#define MSM_R1CS_COEF_STD   0u  /* value = coefficient, plain integer                           */
+#define MSM_R1CS_COEF_MONT  1u  /* value = coefficient * 2^256 mod r  (arkworks Fr.0)           */
+#define MSM_R1CS_COEF_MONT2 2u  /* value = coefficient * 2^512 mod r  (section 4 of a snarkjs zkey) */
+#define MSM_R1CS_C_FROM_AB  8u  /* eval flag: c[i] = a[i]*b[i]; without it c = (matrix 2)*w     */
+
+typedef struct { uint32_t matrix, row, col; uint32_t value[8]; } msm_r1cs_coef_t;  /* 44 bytes, no padding */
+
+/* what an upload builds.  Rows are cut into work items of at most max_item_len <= 24 entries, one GPU lane each (24 additions of a raw 256-bit
+ * word or of 7r minus one stay below the 2^261 the lazily reduced sum can hold); a row of several items has its partial sums folded by a second
+ * launch.  A row without entries, in a matrix that has any, is a work item of length 0. */
+typedef struct {
+    uint64_t entries[3];           /* per matrix                                                     */
+    uint64_t rows_with_entries[3];
+    uint64_t longest_row;          /* entries                                                        */
+    uint64_t plus_one, minus_one;  /* entries whose coefficient is 1 / r - 1 (modulo r): no multiplication */
+    uint64_t distinct_values;      /* the other coefficients' dictionary                             */
+    uint64_t work_items, max_item_len;
+    uint64_t fold_rows;            /* rows of more than one item ...                                 */
+    uint64_t partial_sums;         /* ... and their items                                            */
+    uint64_t device_bytes;
+    double build_ms;               /* host: validation, the counting sort by (matrix, row), the dictionary, the layout */
+    double upload_ms;              /* the whole upload call, build_ms included (0 from msm_bn254_fr_r1cs_plan)          */
+} msm_r1cs_info_t;
+
+/* host only, no context, no GPU: validates the list as the upload does (same errors; the message, msm_last_error(NULL), names the first offending
+ * entry) and reports what an upload would build.  The coefficient values are taken as MSM_R1CS_COEF_STD. */
+int32_t msm_bn254_fr_r1cs_plan(const msm_r1cs_coef_t *coefs, size_t n_coefs, uint32_t num_rows, uint32_t num_cols, uint32_t log_n,
+                               msm_r1cs_info_t *out);
+/* builds the resident form of up to three matrices (matrix 0, 1, 2 = A, B, C) of num_rows x num_cols on the context, replacing an earlier one;
+ * blocks until it is resident.  The evaluations are laid out over a domain of 2^log_n >= num_rows rows.
+ * Errors: n_coefs == 0: MSM_ERR_EMPTY; matrix > 2, row >= num_rows, col >= num_cols, num_rows > 2^log_n, log_n > 28, a bad form:
+ * MSM_ERR_BAD_ARG.  After an error the context stays usable and keeps what it held. */
+int32_t msm_bn254_fr_r1cs_upload(msm_ctx *ctx, const msm_r1cs_coef_t *coefs, size_t n_coefs, uint32_t coef_form, uint32_t num_rows,
+                                 uint32_t num_cols, uint32_t log_n);
+/* what the context's latest upload built and how long it took; MSM_ERR_STATE without one */
+int32_t msm_bn254_fr_r1cs_info(msm_ctx *ctx, msm_r1cs_info_t *out);
+/* d_witness: n_witness = num_cols elements of 8 words; d_out: 3 x 2^log_n elements, written as [a | b | c] -- every row at or above num_rows and
+ * every row without entries as zero.  Both in device memory, 16-byte aligned.  flags: MSM_NTT_IN_MONT (the witness words are w*2^256),
+ * MSM_NTT_OUT_MONT (the output words likewise), MSM_R1CS_C_FROM_AB.  Outputs are canonical (< r).
+ * Stream-ordered on hip_stream (NULL = the context's stream): returns when enqueued.  Rows of more than 24 entries go through a per-context
+ * array of partial sums: an eval on another stream than the one before it waits for that one.
+ * Errors: no upload: MSM_ERR_STATE; n_witness != num_cols, an unknown flag bit, a NULL or misaligned pointer: MSM_ERR_BAD_ARG. */
+int32_t msm_bn254_fr_r1cs_eval_device(msm_ctx *ctx, const void *d_witness, size_t n_witness, void *d_out, uint32_t flags, void *hip_stream);
+/* host pointers, blocking; pageable memory is pinned in place like every host-pointer call */
+int32_t msm_bn254_fr_r1cs_eval(msm_ctx *ctx, const uint32_t *witness, size_t n_witness, uint32_t *out, uint32_t flags);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 /* the plan of a call on n points under (window_bits, flags); with MSM_FLAG_WINDOW_TABLE in flags: the plan of a RESIDENT call on a
  * set of n bases uploaded under those flags (window width, table factor, table memory) */

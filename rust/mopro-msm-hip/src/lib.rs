@@ -109,6 +109,39 @@ pub const NTT_INVERSE: u32 = 1;
 pub const NTT_IN_MONT: u32 = 2;
 pub const NTT_OUT_MONT: u32 = 4;
 
+/// Coefficient forms and the eval flag of the R1CS rows (include/msm_hip.h MSM_R1CS_*)
+pub const R1CS_COEF_STD: u32 = 0;
+pub const R1CS_COEF_MONT: u32 = 1;
+pub const R1CS_COEF_MONT2: u32 = 2;
+pub const R1CS_C_FROM_AB: u32 = 8;
+/// msm_r1cs_coef_t: one entry of a constraint matrix, laid out as an entry of a zkey's coefficient section (44 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MsmR1csCoef {
+    pub matrix: u32,
+    pub row: u32,
+    pub col: u32,
+    pub value: [u32; 8],
+}
+/// msm_r1cs_info_t: what an upload builds
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmR1csInfo {
+    pub entries: [u64; 3],
+    pub rows_with_entries: [u64; 3],
+    pub longest_row: u64,
+    pub plus_one: u64,
+    pub minus_one: u64,
+    pub distinct_values: u64,
+    pub work_items: u64,
+    pub max_item_len: u64,
+    pub fold_rows: u64,
+    pub partial_sums: u64,
+    pub device_bytes: u64,
+    pub build_ms: f64,
+    pub upload_ms: f64,
+}
+
 // The H scalars of a Groth16 proof made in HBM (include/msm_hip.h "BN254 scalar field Fr"): transforms over Fr and the
 // pointwise step between them, in front of msm_bn254_g1_resident_device.  Declarations only, like the G2 loaders above.
 #[allow(dead_code)]
@@ -126,6 +159,18 @@ extern "C" {
         ctx: *mut MsmCtx, d_a: *const core::ffi::c_void, d_b: *const core::ffi::c_void, d_c: *const core::ffi::c_void, k_std: *const u32,
         d_out: *mut core::ffi::c_void, n: usize, flags: u32, hip_stream: *mut core::ffi::c_void,
     ) -> i32;
+    pub fn msm_bn254_fr_r1cs_plan(
+        coefs: *const MsmR1csCoef, n_coefs: usize, num_rows: u32, num_cols: u32, log_n: u32, out: *mut MsmR1csInfo,
+    ) -> i32;
+    pub fn msm_bn254_fr_r1cs_upload(
+        ctx: *mut MsmCtx, coefs: *const MsmR1csCoef, n_coefs: usize, coef_form: u32, num_rows: u32, num_cols: u32, log_n: u32,
+    ) -> i32;
+    pub fn msm_bn254_fr_r1cs_info(ctx: *mut MsmCtx, out: *mut MsmR1csInfo) -> i32;
+    pub fn msm_bn254_fr_r1cs_eval_device(
+        ctx: *mut MsmCtx, d_witness: *const core::ffi::c_void, n_witness: usize, d_out: *mut core::ffi::c_void, flags: u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_r1cs_eval(ctx: *mut MsmCtx, witness: *const u32, n_witness: usize, out: *mut u32, flags: u32) -> i32;
 }
 
 struct Ctx(*mut MsmCtx);
