@@ -47,6 +47,7 @@
 #include "msm_kernels_g2_points.hpp"
 #include "ntt_bn254.hpp"
 #include "r1cs_bn254.hpp"
+#include "msm_kernels_fixed_base.hpp"
 
 namespace {
 
@@ -169,6 +170,7 @@ struct Knobs {
 constexpr int STREAM_SLOTS = 3;
 struct NttState;  // msm_ntt.inc
 struct R1csState;  // msm_r1cs.inc
+struct FixedBaseState;  // msm_fixed_base.inc
 struct msm_ctx {
     std::mutex mu;
     Knobs knobs;
@@ -229,12 +231,14 @@ struct msm_ctx {
     bool no_host_pin = false;     // a context of an msm_multi handle: the handle pins the caller's arrays once for all its ranks (HostPin)
     NttState* ntt = nullptr;      // tables and scratch of the scalar-field transforms, made by the first of them (msm_ntt.inc)
     R1csState* r1cs = nullptr;    // the resident constraint matrices and their scratch, made by the first upload (msm_r1cs.inc)
+    FixedBaseState* fixed_base = nullptr;  // the window table of the latest fixed base, made by the first such call (msm_fixed_base.inc)
 };
 
 namespace {
 
 void ntt_release(msm_ctx* c);  // msm_ntt.inc
 void r1cs_release(msm_ctx* c);  // msm_r1cs.inc
+void fixed_base_release(msm_ctx* c);  // msm_fixed_base.inc
 
 int32_t fail(msm_ctx* c, int32_t code, const char* fmt, ...) {
     char buf[512];
@@ -1561,6 +1565,7 @@ void msm_ctx_destroy(msm_ctx* c) {
         if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
         ntt_release(c);
         r1cs_release(c);
+        fixed_base_release(c);
         DevBuf* bufs[] = {&c->bases,   &c->inf,       &c->scalars, &c->digits,  &c->ranks,  &c->sorted, &c->hist,
                           &c->offsets, &c->blocksums, &c->buckets, &c->rc,      &c->flags,  &c->pow2,
                           &c->sorttmp, &c->tilecounts, &c->ibases, &c->longlist, &c->longdone, &c->midlist, &c->ccounts, &c->cregion, &c->bigslot, &c->big,
@@ -2082,6 +2087,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 #include "msm_g2_points.inc"
 #include "msm_ntt.inc"
 #include "msm_r1cs.inc"
+#include "msm_fixed_base.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS
 #include "msm_testhooks.inc"

@@ -27,6 +27,7 @@ FLAG_DETERMINISTIC = 8  # jacobian_mont is the canonical Z = 1 representative: t
 NTT_INVERSE, NTT_IN_MONT, NTT_OUT_MONT = 1, 2, 4  # MSM_NTT_*: inverse transform (1/n included) / input words are arkworks Fr.0 / output words likewise
 R1CS_COEF_STD, R1CS_COEF_MONT, R1CS_COEF_MONT2 = 0, 1, 2  # MSM_R1CS_COEF_*: a coefficient's words are c / c * 2^256 (arkworks Fr.0) / c * 2^512 (a snarkjs zkey's section 4)
 R1CS_C_FROM_AB = 8  # MSM_R1CS_C_FROM_AB: the eval writes c[i] = a[i] * b[i] instead of (matrix 2) * w
+FB_OUT_STD = 8  # MSM_FB_OUT_STD: the fixed-base products come out in standard form (default: arkworks Montgomery words); NTT_IN_MONT is honoured too
 G2_CHECK_CURVE, G2_CHECK_SUBGROUP = 1, 2  # MSM_G2_CHECK_*: coordinates < p and on the twist / [r]P = O (implies the curve check)
 OK, ERR_EMPTY, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE, ERR_INVALID_DATA = 0, -1, -2, -3, -4, -5, -6, -7
 
@@ -45,6 +46,7 @@ ABI_SYMBOLS = [
     "msm_bn254_g1_validate",
     "msm_bn254_fr_root_of_unity", "msm_bn254_fr_ntt_plan", "msm_bn254_fr_ntt_device", "msm_bn254_fr_ntt", "msm_bn254_fr_mul_sub_scale_device",
     "msm_bn254_fr_r1cs_plan", "msm_bn254_fr_r1cs_upload", "msm_bn254_fr_r1cs_info", "msm_bn254_fr_r1cs_eval_device", "msm_bn254_fr_r1cs_eval",
+    "msm_bn254_g1_fixed_base_plan", "msm_bn254_g1_fixed_base_mul_device", "msm_bn254_g1_fixed_base_mul",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -93,6 +95,15 @@ class R1csInfo(C.Structure):
 
     def as_dict(self):
         return {k: (list(getattr(self, k)) if k in ("entries", "rows_with_entries") else getattr(self, k)) for k, _ in self._fields_}
+
+
+class FixedBasePlan(C.Structure):
+    """msm_fixed_base_plan_t: the window table and the inversion group of a fixed-base multiplication"""
+    _fields_ = [("window_bits", C.c_uint32), ("num_windows", C.c_uint32), ("table_entries", C.c_uint64), ("table_bytes", C.c_uint64),
+                ("inv_group", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 # msm_r1cs_coef_t: matrix, row, col, 8 value words -- 44 bytes, the layout of one entry of a zkey's coefficient section
@@ -182,6 +193,9 @@ def bind_product_abi(L):
     L.msm_bn254_fr_r1cs_info.argtypes = [vp, C.POINTER(R1csInfo)]
     L.msm_bn254_fr_r1cs_eval_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp]
     L.msm_bn254_fr_r1cs_eval.argtypes = [vp, _u32p, C.c_size_t, _u32p, C.c_uint32]
+    L.msm_bn254_g1_fixed_base_plan.argtypes = [C.c_uint32, C.POINTER(FixedBasePlan)]
+    L.msm_bn254_g1_fixed_base_mul_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.msm_bn254_g1_fixed_base_mul.argtypes = [vp, _u32p, C.c_uint32, _u32p, C.c_size_t, C.c_uint32, C.c_uint32, _u32p, _u8p]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -333,6 +347,17 @@ def r1cs_plan(coefs, num_rows, num_cols, log_n):
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_fr_r1cs_plan failed ({rc})")
     return info.as_dict()
+
+
+def fixed_base_plan(window_bits=0):
+    """the window table and the inversion group of a fixed-base multiplication with windows of window_bits (0: the default) as a dict of
+    msm_fixed_base_plan_t (host only: no context, no GPU)"""
+    p = FixedBasePlan()
+    lib = load_library()
+    rc = lib.msm_bn254_g1_fixed_base_plan(window_bits, C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g1_fixed_base_plan failed ({rc})")
+    return p.as_dict()
 
 
 def combine_partials(partials_jacobian_mont, want_affine=True, flags=0):
@@ -680,6 +705,23 @@ class MsmContext:
         out = np.zeros((3 << log_n, 8), np.uint32)
         self._check(self._lib.msm_bn254_fr_r1cs_eval(self._h, _p32(w), w.shape[0], _p32(out), flags))
         return out
+
+    # -- BN254 G1 fixed base: out[i] = k_i * P, one base, n affine points (the queries of a setup made in HBM) ---
+    def fixed_base_mul(self, base, scalars, form=FORM_STD, window_bits=0, flags=0):
+        """host arrays: the base (16 words x, y in `form`) and n x 8 scalar words (any 256-bit patterns; flags NTT_IN_MONT: arkworks Fr.0 words)
+        -> (n x 16 words xy, n bytes inf); the coordinates are arkworks Montgomery words, standard form with FB_OUT_STD"""
+        b, k = _words(base, 16), _words(scalars, 8)
+        xy, inf = np.zeros((k.shape[0], 16), np.uint32), np.zeros(k.shape[0], np.uint8)
+        self._check(self._lib.msm_bn254_g1_fixed_base_mul(self._h, _p32(b), form, _p32(k), k.shape[0], window_bits, flags, _p32(xy),
+                                                          inf.ctypes.data_as(_u8p)))
+        return xy, inf
+
+    def fixed_base_mul_device(self, base, d_scalars, n, d_out_xy, d_out_inf, form=FORM_STD, window_bits=0, flags=0, stream=None):
+        """raw device pointers: n x 8 scalar words in, n x 16 words xy and n bytes inf out; the base is a host array; enqueued on `stream`
+        (None: the context's)"""
+        b = _words(base, 16)
+        self._check(self._lib.msm_bn254_g1_fixed_base_mul_device(self._h, _p32(b), form, d_scalars, n, window_bits, flags, d_out_xy, d_out_inf,
+                                                                 stream))
 
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))

@@ -465,6 +465,44 @@ int32_t msm_bn254_fr_r1cs_eval_device(msm_ctx *ctx, const void *d_witness, size_
 /* host pointers, blocking; pageable memory is pinned in place like every host-pointer call */
 int32_t msm_bn254_fr_r1cs_eval(msm_ctx *ctx, const uint32_t *witness, size_t n_witness, uint32_t *out, uint32_t flags);
 
+/* ---- BN254 G1 fixed-base batch multiplication (ABI 7): out[i] = k_i * P, one base, n scalars, n affine points -- the shape of
+ *      arkworks' FixedBase::msm / batch_mul: the A, B1, L and H queries of a Groth16 setup, the powers of a KZG setup.
+ *      A scalar is ANY 256-bit pattern, read as an integer: k * P is (k mod r) * P, as the transforms and the R1CS rows read their inputs.  There is
+ *      no range check and nothing comes back from the device, so the device form is stream-ordered.  With MSM_NTT_IN_MONT the words are arkworks
+ *      Fr.0 (k * 2^256 mod r) and one multiplication by a constant brings them to canonical standard form first.
+ *      Output coordinates are canonical (< p): results are bit-exact.  k_i * P = the identity: out_inf[i] = 1 and all sixteen words zero.
+ *      The base is checked on the host: coordinates < p and y^2 = x^3 + 3, else MSM_ERR_INVALID_DATA.
+ *      The window table of (base, window_bits) -- W * 2^(c-1) affine records of 64 bytes, 2.9 MB at the default c = 12, 270 KB at c = 8 -- is built on the device, on the call's
+ *      stream, and kept on the context; it is rebuilt only when the base (compared after normalising its form) or c changes.  Table and events are
+ *      per context: a call on another stream than the one before it waits for that one.  The inv_group points of a workgroup share ONE field
+ *      inversion (Montgomery's trick in the workgroup's LDS): no scratch array in HBM exists, and a call of any n is cut into launches of at most
+ *      2^30 points.  The host-pointer form stages at most 2^20 points (97 MB of device memory) at a time.
+ *      Errors: base off the curve or a coordinate >= p: MSM_ERR_INVALID_DATA; n == 0: MSM_ERR_EMPTY; a NULL or misaligned pointer, a bad form, an
+ *      unknown flag bit, window_bits not 0 or 4..16: MSM_ERR_BAD_ARG; allocation failure: MSM_ERR_OOM.  The context stays usable after any. ---- */
+#define MSM_FB_OUT_STD 8u   /* output coordinates in standard form; default: arkworks Montgomery words (what msm_bn254_g1_device /
+                               _upload_bases(MSM_FORM_MONT) take) */
+/* MSM_NTT_IN_MONT (2u) is honoured too: scalar words are arkworks Fr.0 (k*2^256 mod r) */
+
+typedef struct {
+    uint32_t window_bits;   /* c */
+    uint32_t num_windows;   /* W = ceil(257 / c): signed digits of a 256-bit integer may carry one bit out */
+    uint64_t table_entries; /* W * 2^(c-1) */
+    uint64_t table_bytes;
+    uint32_t inv_group;     /* points that share one field inversion */
+    uint32_t reserved;
+} msm_fixed_base_plan_t;
+
+/* host only, no context: window_bits 0 = the default; 4..16 otherwise, anything else MSM_ERR_BAD_ARG */
+int32_t msm_bn254_g1_fixed_base_plan(uint32_t window_bits, msm_fixed_base_plan_t *out);
+
+/* out[i] = k_i * P.  base_xy: HOST pointer, 16 words (x, y), base_form MSM_FORM_STD / _MONT; d_scalars: n x 8 words;
+ * d_out_xy: n x 16 words; d_out_inf: n bytes (1 = k_i * P is the identity, coordinates all zero) -- device memory, 16-byte aligned.
+ * Stream-ordered on hip_stream (NULL = the context's stream): returns when enqueued.  Blocking host-pointer form below. */
+int32_t msm_bn254_g1_fixed_base_mul_device(msm_ctx *ctx, const uint32_t *base_xy, uint32_t base_form, const void *d_scalars, size_t n,
+                                           uint32_t window_bits, uint32_t flags, void *d_out_xy, void *d_out_inf, void *hip_stream);
+int32_t msm_bn254_g1_fixed_base_mul(msm_ctx *ctx, const uint32_t *base_xy, uint32_t base_form, const uint32_t *scalars, size_t n,
+                                    uint32_t window_bits, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 /* the plan of a call on n points under (window_bits, flags); with MSM_FLAG_WINDOW_TABLE in flags: the plan of a RESIDENT call on a
  * set of n bases uploaded under those flags (window width, table factor, table memory) */

@@ -173,6 +173,35 @@ extern "C" {
     pub fn msm_bn254_fr_r1cs_eval(ctx: *mut MsmCtx, witness: *const u32, n_witness: usize, out: *mut u32, flags: u32) -> i32;
 }
 
+/// Output form of the fixed-base products (include/msm_hip.h MSM_FB_OUT_STD); NTT_IN_MONT is honoured for the scalars
+pub const FB_OUT_STD: u32 = 8;
+/// msm_fixed_base_plan_t: the window table and the inversion group of a fixed-base multiplication
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmFixedBasePlan {
+    pub window_bits: u32,
+    pub num_windows: u32,
+    pub table_entries: u64,
+    pub table_bytes: u64,
+    pub inv_group: u32,
+    pub reserved: u32,
+}
+
+// out[i] = k_i * P made in HBM (include/msm_hip.h "fixed-base batch multiplication"): the bases of a setup in front of
+// msm_bn254_g1_upload_bases / msm_bn254_g1_device.  Declarations only, like the transforms above.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_g1_fixed_base_plan(window_bits: u32, out: *mut MsmFixedBasePlan) -> i32;
+    pub fn msm_bn254_g1_fixed_base_mul_device(
+        ctx: *mut MsmCtx, base_xy: *const u32, base_form: u32, d_scalars: *const core::ffi::c_void, n: usize, window_bits: u32, flags: u32,
+        d_out_xy: *mut core::ffi::c_void, d_out_inf: *mut core::ffi::c_void, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_g1_fixed_base_mul(
+        ctx: *mut MsmCtx, base_xy: *const u32, base_form: u32, scalars: *const u32, n: usize, window_bits: u32, flags: u32, out_xy: *mut u32,
+        out_inf: *mut u8,
+    ) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 
