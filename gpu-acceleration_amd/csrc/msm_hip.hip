@@ -48,6 +48,7 @@
 #include "ntt_bn254.hpp"
 #include "r1cs_bn254.hpp"
 #include "msm_kernels_fixed_base.hpp"
+#include "msm_kernels_fixed_base_g2.hpp"
 
 namespace {
 
@@ -124,6 +125,7 @@ struct Knobs {
     uint32_t stream_chunk_log2 = 0;            // MSM_HIP_STREAM_CHUNK_LOG2: 0 = by size (product: msm_config_t.stream_chunk_log2)
     std::vector<uint32_t> stream_schedule;     // MSM_HIP_STREAM_SCHEDULE="17,18,18,18,17": the chunks of a streamed host call as log2 sizes, used when they sum to n (tools/host_schedule_sweep.py)
     int host_threads = -1;                     // MSM_HIP_HOST_THREADS: CPU finish threads incl. the caller; -1 = msm_config_t.host_threads
+    uint32_t fb2_inv_group = 0;                // MSM_HIP_FB2_INV_GROUP: points per chain of k_fb2_normalise; 0 = the plan's (tools/fixed_base_g2_timing.py)
     msmplan::table_knobs table;                // MSM_HIP_TABLE_C / MSM_HIP_TABLE_F / MSM_HIP_TABLE_MAX_GB / MSM_HIP_TABLE_GLV_MAX_LOG2 (window table of a resident set)
     static Knobs from_env() {
         Knobs k;
@@ -155,6 +157,7 @@ struct Knobs {
             }
         }
         if (std::getenv("MSM_HIP_HOST_THREADS")) k.host_threads = (int)num("MSM_HIP_HOST_THREADS", 0, 64, 2);
+        k.fb2_inv_group = (uint32_t)num("MSM_HIP_FB2_INV_GROUP", 0, 64, 0);
         k.table.c = (uint32_t)num("MSM_HIP_TABLE_C", 0, 20, 0);
         k.table.f = (uint32_t)num("MSM_HIP_TABLE_F", 0, 128, 0);
         k.table.max_bytes = (size_t)num("MSM_HIP_TABLE_MAX_GB", 0, 1024, 64) << 30;
@@ -171,6 +174,7 @@ constexpr int STREAM_SLOTS = 3;
 struct NttState;  // msm_ntt.inc
 struct R1csState;  // msm_r1cs.inc
 struct FixedBaseState;  // msm_fixed_base.inc
+struct FixedBaseG2State;  // msm_fixed_base_g2.inc
 struct msm_ctx {
     std::mutex mu;
     Knobs knobs;
@@ -232,6 +236,7 @@ struct msm_ctx {
     NttState* ntt = nullptr;      // tables and scratch of the scalar-field transforms, made by the first of them (msm_ntt.inc)
     R1csState* r1cs = nullptr;    // the resident constraint matrices and their scratch, made by the first upload (msm_r1cs.inc)
     FixedBaseState* fixed_base = nullptr;  // the window table of the latest fixed base, made by the first such call (msm_fixed_base.inc)
+    FixedBaseG2State* fixed_base_g2 = nullptr;  // the same for G2, with the scratch array of its two-kernel chunks (msm_fixed_base_g2.inc)
 };
 
 namespace {
@@ -239,6 +244,7 @@ namespace {
 void ntt_release(msm_ctx* c);  // msm_ntt.inc
 void r1cs_release(msm_ctx* c);  // msm_r1cs.inc
 void fixed_base_release(msm_ctx* c);  // msm_fixed_base.inc
+void fixed_base_g2_release(msm_ctx* c);  // msm_fixed_base_g2.inc
 
 int32_t fail(msm_ctx* c, int32_t code, const char* fmt, ...) {
     char buf[512];
@@ -1566,6 +1572,7 @@ void msm_ctx_destroy(msm_ctx* c) {
         ntt_release(c);
         r1cs_release(c);
         fixed_base_release(c);
+        fixed_base_g2_release(c);
         DevBuf* bufs[] = {&c->bases,   &c->inf,       &c->scalars, &c->digits,  &c->ranks,  &c->sorted, &c->hist,
                           &c->offsets, &c->blocksums, &c->buckets, &c->rc,      &c->flags,  &c->pow2,
                           &c->sorttmp, &c->tilecounts, &c->ibases, &c->longlist, &c->longdone, &c->midlist, &c->ccounts, &c->cregion, &c->bigslot, &c->big,
@@ -2088,6 +2095,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 #include "msm_ntt.inc"
 #include "msm_r1cs.inc"
 #include "msm_fixed_base.inc"
+#include "msm_fixed_base_g2.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS
 #include "msm_testhooks.inc"

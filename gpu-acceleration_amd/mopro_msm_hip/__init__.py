@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "msm_bn254_fr_root_of_unity", "msm_bn254_fr_ntt_plan", "msm_bn254_fr_ntt_device", "msm_bn254_fr_ntt", "msm_bn254_fr_mul_sub_scale_device",
     "msm_bn254_fr_r1cs_plan", "msm_bn254_fr_r1cs_upload", "msm_bn254_fr_r1cs_info", "msm_bn254_fr_r1cs_eval_device", "msm_bn254_fr_r1cs_eval",
     "msm_bn254_g1_fixed_base_plan", "msm_bn254_g1_fixed_base_mul_device", "msm_bn254_g1_fixed_base_mul",
+    "msm_bn254_g2_fixed_base_plan", "msm_bn254_g2_fixed_base_mul_device", "msm_bn254_g2_fixed_base_mul",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -104,6 +105,15 @@ class FixedBasePlan(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class FixedBaseG2Plan(C.Structure):
+    """msm_fixed_base_g2_plan_t: the window table, the inversion group and the scratch array of a G2 fixed-base multiplication"""
+    _fields_ = [("window_bits", C.c_uint32), ("num_windows", C.c_uint32), ("table_entries", C.c_uint64), ("table_bytes", C.c_uint64),
+                ("inv_group", C.c_uint32), ("chunk_points", C.c_uint32), ("scratch_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # msm_r1cs_coef_t: matrix, row, col, 8 value words -- 44 bytes, the layout of one entry of a zkey's coefficient section
@@ -196,6 +206,9 @@ def bind_product_abi(L):
     L.msm_bn254_g1_fixed_base_plan.argtypes = [C.c_uint32, C.POINTER(FixedBasePlan)]
     L.msm_bn254_g1_fixed_base_mul_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.msm_bn254_g1_fixed_base_mul.argtypes = [vp, _u32p, C.c_uint32, _u32p, C.c_size_t, C.c_uint32, C.c_uint32, _u32p, _u8p]
+    L.msm_bn254_g2_fixed_base_plan.argtypes = [C.c_uint32, C.POINTER(FixedBaseG2Plan)]
+    L.msm_bn254_g2_fixed_base_mul_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.msm_bn254_g2_fixed_base_mul.argtypes = [vp, _u32p, C.c_uint32, _u32p, C.c_size_t, C.c_uint32, C.c_uint32, _u32p, _u8p]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -357,6 +370,17 @@ def fixed_base_plan(window_bits=0):
     rc = lib.msm_bn254_g1_fixed_base_plan(window_bits, C.byref(p))
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g1_fixed_base_plan failed ({rc})")
+    return p.as_dict()
+
+
+def fixed_base_g2_plan(window_bits=0):
+    """the same for the G2 call, with the points of a chunk and the scratch array they go through, as a dict of msm_fixed_base_g2_plan_t
+    (host only: no context, no GPU)"""
+    p = FixedBaseG2Plan()
+    lib = load_library()
+    rc = lib.msm_bn254_g2_fixed_base_plan(window_bits, C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g2_fixed_base_plan failed ({rc})")
     return p.as_dict()
 
 
@@ -721,6 +745,23 @@ class MsmContext:
         (None: the context's)"""
         b = _words(base, 16)
         self._check(self._lib.msm_bn254_g1_fixed_base_mul_device(self._h, _p32(b), form, d_scalars, n, window_bits, flags, d_out_xy, d_out_inf,
+                                                                 stream))
+
+    # -- BN254 G2 fixed base: out[i] = k_i * Q (the B2 query of a setup); the base is checked on the host: on the twist, and in G2 ---
+    def fixed_base_g2_mul(self, base, scalars, form=FORM_STD, window_bits=0, flags=0):
+        """host arrays: the base (32 words x.c0, x.c1, y.c0, y.c1 in `form`) and n x 8 scalar words (flags NTT_IN_MONT: arkworks Fr.0 words)
+        -> (n x 32 words xy, n bytes inf); the coordinates are arkworks Montgomery words, standard form with FB_OUT_STD"""
+        b, k = _words(base, 32), _words(scalars, 8)
+        xy, inf = np.zeros((k.shape[0], 32), np.uint32), np.zeros(k.shape[0], np.uint8)
+        self._check(self._lib.msm_bn254_g2_fixed_base_mul(self._h, _p32(b), form, _p32(k), k.shape[0], window_bits, flags, _p32(xy),
+                                                          inf.ctypes.data_as(_u8p)))
+        return xy, inf
+
+    def fixed_base_g2_mul_device(self, base, d_scalars, n, d_out_xy, d_out_inf, form=FORM_STD, window_bits=0, flags=0, stream=None):
+        """raw device pointers: n x 8 scalar words in, n x 32 words xy and n bytes inf out (what msm_g2_device takes); the base is a host
+        array; enqueued on `stream` (None: the context's)"""
+        b = _words(base, 32)
+        self._check(self._lib.msm_bn254_g2_fixed_base_mul_device(self._h, _p32(b), form, d_scalars, n, window_bits, flags, d_out_xy, d_out_inf,
                                                                  stream))
 
     def set_stage_timing(self, enabled=True):

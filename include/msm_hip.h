@@ -503,6 +503,40 @@ int32_t msm_bn254_g1_fixed_base_mul_device(msm_ctx *ctx, const uint32_t *base_xy
 int32_t msm_bn254_g1_fixed_base_mul(msm_ctx *ctx, const uint32_t *base_xy, uint32_t base_form, const uint32_t *scalars, size_t n,
                                     uint32_t window_bits, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
 
+/* ---- BN254 G2 fixed-base batch multiplication (ABI 7): out[i] = k_i * Q for one base Q of G2, n scalars, n affine points of
+ *      32 words (x.c0, x.c1, y.c0, y.c1) -- the B2 query of a Groth16 setup (k_i * H), the G2 powers of a KZG setup.  Scalars, flags
+ *      (MSM_NTT_IN_MONT, MSM_FB_OUT_STD), output forms, the infinity bytes (k_i = 0 mod r: out_inf[i] = 1 and all 32 words zero) and the
+ *      errors are those of the G1 call above; the outputs are what msm_bn254_g2_device takes as d_bases_mont / d_inf_mask.
+ *      The base is checked on the host every call: components < p and y^2 = x^3 + 3/(9+u) ("curve" in msm_last_error), and, whenever it is not
+ *      the base the context's table was built from, [r]Q = O ("subgroup") -- the twist's cofactor is not 1, and reading a 256-bit scalar as
+ *      (k mod r) is only right in G2.  Either failure: MSM_ERR_INVALID_DATA, and the table of the previous base stays in place.
+ *      The window table of (base, window_bits) -- W * 2^(c-1) affine records of 128 bytes, 5.8 MB at the default c = 12 -- is built on the device,
+ *      on the call's stream, and kept on the context beside (not instead of) the G1 call's table; it is rebuilt only when the base (compared as
+ *      Montgomery words) or c changes.  The products of a chunk of chunk_points scalars go through a per-context array of XYZZ records
+ *      (scratch_bytes) and are normalised by a second kernel in which every lane inverts a chain of inv_group points with ONE field inversion;
+ *      a call of any n is cut into such chunks.  Table, scratch array and event are per context: a call on another stream than the one before
+ *      it waits for that one.  The host-pointer form stages chunk_points points (42 MB of device memory) at a time. ---- */
+typedef struct {
+    uint32_t window_bits;   /* c */
+    uint32_t num_windows;   /* W = ceil(257 / c) */
+    uint64_t table_entries; /* W * 2^(c-1) */
+    uint64_t table_bytes;   /* records of 128 bytes */
+    uint32_t inv_group;     /* points that share one field inversion */
+    uint32_t chunk_points;  /* points per pass through the scratch array (device form) and per staging step (host form) */
+    uint64_t scratch_bytes; /* the per-context XYZZ scratch array of one chunk */
+} msm_fixed_base_g2_plan_t;
+
+/* host only, no context: window_bits 0 = the default; 4..16 otherwise, anything else MSM_ERR_BAD_ARG */
+int32_t msm_bn254_g2_fixed_base_plan(uint32_t window_bits, msm_fixed_base_g2_plan_t *out);
+
+/* out[i] = k_i * Q.  base_xy: HOST pointer, 32 words, base_form MSM_FORM_STD / _MONT; d_scalars: n x 8 words; d_out_xy: n x 32 words;
+ * d_out_inf: n bytes -- device memory, 16-byte aligned.  Stream-ordered on hip_stream (NULL = the context's stream): returns when enqueued.
+ * Blocking host-pointer form below. */
+int32_t msm_bn254_g2_fixed_base_mul_device(msm_ctx *ctx, const uint32_t *base_xy, uint32_t base_form, const void *d_scalars, size_t n,
+                                           uint32_t window_bits, uint32_t flags, void *d_out_xy, void *d_out_inf, void *hip_stream);
+int32_t msm_bn254_g2_fixed_base_mul(msm_ctx *ctx, const uint32_t *base_xy, uint32_t base_form, const uint32_t *scalars, size_t n,
+                                    uint32_t window_bits, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 /* the plan of a call on n points under (window_bits, flags); with MSM_FLAG_WINDOW_TABLE in flags: the plan of a RESIDENT call on a
  * set of n bases uploaded under those flags (window width, table factor, table memory) */

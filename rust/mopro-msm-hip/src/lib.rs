@@ -202,6 +202,33 @@ extern "C" {
     ) -> i32;
 }
 
+/// msm_fixed_base_g2_plan_t: the same for G2, with the points of a chunk and the scratch array they go through
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmFixedBaseG2Plan {
+    pub window_bits: u32,
+    pub num_windows: u32,
+    pub table_entries: u64,
+    pub table_bytes: u64,
+    pub inv_group: u32,
+    pub chunk_points: u32,
+    pub scratch_bytes: u64,
+}
+
+// out[i] = k_i * Q on G2 (the B2 query of a setup): 32 words per base and per output, what msm_bn254_g2_device takes.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_g2_fixed_base_plan(window_bits: u32, out: *mut MsmFixedBaseG2Plan) -> i32;
+    pub fn msm_bn254_g2_fixed_base_mul_device(
+        ctx: *mut MsmCtx, base_xy: *const u32, base_form: u32, d_scalars: *const core::ffi::c_void, n: usize, window_bits: u32, flags: u32,
+        d_out_xy: *mut core::ffi::c_void, d_out_inf: *mut core::ffi::c_void, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_g2_fixed_base_mul(
+        ctx: *mut MsmCtx, base_xy: *const u32, base_form: u32, scalars: *const u32, n: usize, window_bits: u32, flags: u32, out_xy: *mut u32,
+        out_inf: *mut u8,
+    ) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 
