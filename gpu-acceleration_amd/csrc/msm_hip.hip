@@ -49,6 +49,7 @@
 #include "r1cs_bn254.hpp"
 #include "msm_kernels_fixed_base.hpp"
 #include "msm_kernels_fixed_base_g2.hpp"
+#include "fr_vectors_bn254.hpp"
 
 namespace {
 
@@ -126,6 +127,7 @@ struct Knobs {
     std::vector<uint32_t> stream_schedule;     // MSM_HIP_STREAM_SCHEDULE="17,18,18,18,17": the chunks of a streamed host call as log2 sizes, used when they sum to n (tools/host_schedule_sweep.py)
     int host_threads = -1;                     // MSM_HIP_HOST_THREADS: CPU finish threads incl. the caller; -1 = msm_config_t.host_threads
     uint32_t fb2_inv_group = 0;                // MSM_HIP_FB2_INV_GROUP: points per chain of k_fb2_normalise; 0 = the plan's (tools/fixed_base_g2_timing.py)
+    uint32_t frv_inv_group = 0;                // MSM_HIP_FRV_INV_GROUP: elements per chain of k_frv_batch_inverse (4, 8, 16, 32); 0 = the plan's (tools/fr_vectors_timing.py)
     msmplan::table_knobs table;                // MSM_HIP_TABLE_C / MSM_HIP_TABLE_F / MSM_HIP_TABLE_MAX_GB / MSM_HIP_TABLE_GLV_MAX_LOG2 (window table of a resident set)
     static Knobs from_env() {
         Knobs k;
@@ -158,6 +160,7 @@ struct Knobs {
         }
         if (std::getenv("MSM_HIP_HOST_THREADS")) k.host_threads = (int)num("MSM_HIP_HOST_THREADS", 0, 64, 2);
         k.fb2_inv_group = (uint32_t)num("MSM_HIP_FB2_INV_GROUP", 0, 64, 0);
+        k.frv_inv_group = (uint32_t)num("MSM_HIP_FRV_INV_GROUP", 0, 32, 0);
         k.table.c = (uint32_t)num("MSM_HIP_TABLE_C", 0, 20, 0);
         k.table.f = (uint32_t)num("MSM_HIP_TABLE_F", 0, 128, 0);
         k.table.max_bytes = (size_t)num("MSM_HIP_TABLE_MAX_GB", 0, 1024, 64) << 30;
@@ -2096,6 +2099,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 #include "msm_r1cs.inc"
 #include "msm_fixed_base.inc"
 #include "msm_fixed_base_g2.inc"
+#include "msm_fr_vectors.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS
 #include "msm_testhooks.inc"

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "msm_bn254_fr_r1cs_plan", "msm_bn254_fr_r1cs_upload", "msm_bn254_fr_r1cs_info", "msm_bn254_fr_r1cs_eval_device", "msm_bn254_fr_r1cs_eval",
     "msm_bn254_g1_fixed_base_plan", "msm_bn254_g1_fixed_base_mul_device", "msm_bn254_g1_fixed_base_mul",
     "msm_bn254_g2_fixed_base_plan", "msm_bn254_g2_fixed_base_mul_device", "msm_bn254_g2_fixed_base_mul",
+    "msm_bn254_fr_vector_plan", "msm_bn254_fr_powers_device", "msm_bn254_fr_batch_inverse_device", "msm_bn254_fr_batch_inverse",
+    "msm_bn254_fr_lagrange_device", "msm_bn254_fr_lincomb_device",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -114,6 +116,14 @@ class FixedBaseG2Plan(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FrVectorPlan(C.Structure):
+    """msm_fr_vector_plan_t: the inversion group and the elements a workgroup covers in the scalar-vector calls"""
+    _fields_ = [("inv_group", C.c_uint32), ("block_points", C.c_uint32), ("powers_block_points", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 # msm_r1cs_coef_t: matrix, row, col, 8 value words -- 44 bytes, the layout of one entry of a zkey's coefficient section
@@ -209,6 +219,12 @@ def bind_product_abi(L):
     L.msm_bn254_g2_fixed_base_plan.argtypes = [C.c_uint32, C.POINTER(FixedBaseG2Plan)]
     L.msm_bn254_g2_fixed_base_mul_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.msm_bn254_g2_fixed_base_mul.argtypes = [vp, _u32p, C.c_uint32, _u32p, C.c_size_t, C.c_uint32, C.c_uint32, _u32p, _u8p]
+    L.msm_bn254_fr_vector_plan.argtypes = [C.POINTER(FrVectorPlan)]
+    L.msm_bn254_fr_powers_device.argtypes = [vp, _u32p, _u32p, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp]
+    L.msm_bn254_fr_batch_inverse_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+    L.msm_bn254_fr_batch_inverse.argtypes = [vp, _u32p, _u32p, C.c_size_t, C.c_uint32]
+    L.msm_bn254_fr_lagrange_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_uint32, vp]
+    L.msm_bn254_fr_lincomb_device.argtypes = [vp, vp, _u32p, vp, _u32p, vp, _u32p, vp, C.c_size_t, C.c_uint32, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -360,6 +376,24 @@ def r1cs_plan(coefs, num_rows, num_cols, log_n):
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_fr_r1cs_plan failed ({rc})")
     return info.as_dict()
+
+
+def transpose_r1cs_coefs(coefs):
+    """the same entries with row and col swapped: uploaded with num_rows' = n_vars, num_cols' = 2^log_n, log_n' = ceil(log2 n_vars), an eval on
+    the Lagrange vector gives [a_j(tau) | b_j(tau) | c_j(tau)] per variable j -- the QAP polynomials of a setup"""
+    t = r1cs_coefs(coefs).copy()
+    t["row"], t["col"] = t["col"].copy(), t["row"].copy()
+    return t
+
+
+def fr_vector_plan():
+    """the inversion group and the elements one workgroup covers in the scalar-vector calls, as a dict of msm_fr_vector_plan_t (host only)"""
+    p = FrVectorPlan()
+    lib = load_library()
+    rc = lib.msm_bn254_fr_vector_plan(C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_fr_vector_plan failed ({rc})")
+    return p.as_dict()
 
 
 def fixed_base_plan(window_bits=0):
@@ -729,6 +763,43 @@ class MsmContext:
         out = np.zeros((3 << log_n, 8), np.uint32)
         self._check(self._lib.msm_bn254_fr_r1cs_eval(self._h, _p32(w), w.shape[0], _p32(out), flags))
         return out
+
+    # -- BN254 scalar field: the scalars of a setup made in HBM (what the fixed-base calls read); nothing is kept on the context ---
+    def fr_powers_device(self, base, d_out, n, scale=None, first=0, flags=0, stream=None):
+        """out[i] = scale * base^(first + i) on a raw device pointer; base, scale: ints or 8 standard-form words (scale None: 1); flags
+        NTT_OUT_MONT; enqueued on `stream` (None: the context's)"""
+        self._check(self._lib.msm_bn254_fr_powers_device(self._h, _p32(_fr_words(base)), _p32(_fr_words(scale)), first, d_out, n, flags, stream))
+
+    def fr_batch_inverse_device(self, d_in, d_out, n, flags=0, stream=None):
+        """out[i] = 1 / in[i] on raw device pointers (0 stays 0; d_out may be d_in); flags NTT_IN_MONT / NTT_OUT_MONT"""
+        self._check(self._lib.msm_bn254_fr_batch_inverse_device(self._h, d_in, d_out, n, flags, stream))
+
+    def fr_batch_inverse(self, values, flags=0, out=None):
+        """host arrays: n x 8 words -> their inverses, a new array or `out` (a contiguous uint32 array, which may be `values` itself)"""
+        a = _words(values, 8)
+        if out is None:
+            out = np.zeros_like(a)
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.flags.c_contiguous and out.size == a.size):
+                raise MsmError(ERR_BAD_ARG, "out must be a contiguous uint32 array of the input's size")
+            out = out.reshape(-1, 8)
+        self._check(self._lib.msm_bn254_fr_batch_inverse(self._h, _p32(a), _p32(out), a.shape[0], flags))
+        return out
+
+    def fr_lagrange_device(self, tau, log_n, d_out, flags=0, stream=None):
+        """out[i] = L_i(tau) over the transforms' domain of 2^log_n points on a raw device pointer; tau: an int or 8 standard-form words; flags
+        NTT_OUT_MONT"""
+        self._check(self._lib.msm_bn254_fr_lagrange_device(self._h, _p32(_fr_words(tau)), log_n, d_out, flags, stream))
+
+    def fr_lincomb_device(self, d_a, d_out, n, ka=None, d_b=None, kb=None, d_c=None, kc=None, flags=0, stream=None):
+        """out[i] = ka a[i] + kb b[i] + kc c[i] on raw device pointers; d_b / d_c None: no such term; a coefficient None: 1; d_out may alias an
+        input; flags NTT_IN_MONT / NTT_OUT_MONT"""
+        self._check(self._lib.msm_bn254_fr_lincomb_device(self._h, d_a, _p32(_fr_words(ka)), d_b, _p32(_fr_words(kb)), d_c, _p32(_fr_words(kc)),
+                                                          d_out, n, flags, stream))
+
+    @staticmethod
+    def fr_vector_plan():
+        return fr_vector_plan()
 
     # -- BN254 G1 fixed base: out[i] = k_i * P, one base, n affine points (the queries of a setup made in HBM) ---
     def fixed_base_mul(self, base, scalars, form=FORM_STD, window_bits=0, flags=0):

@@ -537,6 +537,40 @@ int32_t msm_bn254_g2_fixed_base_mul_device(msm_ctx *ctx, const uint32_t *base_xy
 int32_t msm_bn254_g2_fixed_base_mul(msm_ctx *ctx, const uint32_t *base_xy, uint32_t base_form, const uint32_t *scalars, size_t n,
                                     uint32_t window_bits, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
 
+/* ---- BN254 scalar field Fr: the scalars of a setup made in HBM (ABI 7) -- what the fixed-base calls above read as k_i:
+ *      powers of tau (the H query, KZG), element-wise inverses, the Lagrange coefficients L_i(tau) of the transforms' domain, and the linear
+ *      combination of the L query.  Conventions of msm_bn254_fr_ntt_device: elements are 8 little-endian words; any 256-bit input pattern is
+ *      read modulo r; outputs are canonical (< r), so results are bit-exact; MSM_NTT_IN_MONT / MSM_NTT_OUT_MONT name the form of the DEVICE
+ *      arrays (arkworks Fr.0; standard form by default).  tau, base, scale and the coefficients are HOST pointers to 8 standard-form words, read
+ *      modulo r.  Device arrays are 16-byte aligned.  Stream-ordered on hip_stream (NULL = the context's stream): a call returns when enqueued.
+ *      UNLIKE the transforms, these calls keep nothing on the context -- no table, no scratch array, no event; every constant travels with the
+ *      kernel launch -- so two calls on two streams do NOT wait for each other, and the caller orders calls that share an array.
+ *      Errors: a NULL or misaligned pointer, an unknown flag bit, n > 2^36: MSM_ERR_BAD_ARG; n == 0: MSM_ERR_EMPTY; allocation failure (host
+ *      form): MSM_ERR_OOM.  The context stays usable after any of them. ---- */
+typedef struct {
+    uint32_t inv_group;            /* elements that share one field inversion (a chain of the inverse and Lagrange kernels) */
+    uint32_t block_points;         /* consecutive elements one workgroup of those kernels covers: 256 * inv_group */
+    uint32_t powers_block_points;  /* ... one workgroup of the powers kernel */
+    uint32_t reserved;
+} msm_fr_vector_plan_t;
+/* host only, no context */
+int32_t msm_bn254_fr_vector_plan(msm_fr_vector_plan_t *out);
+/* out[i] = scale * base^(first + i), i < n.  scale_std NULL = 1.  0^0 = 1: base = 0 gives out[0] = scale when first == 0 and 0 elsewhere.
+ * flags: MSM_NTT_OUT_MONT only.  first + n must not exceed 2^64.  About two field multiplications per element. */
+int32_t msm_bn254_fr_powers_device(msm_ctx *ctx, const uint32_t *base_std, const uint32_t *scale_std, uint64_t first, void *d_out, size_t n,
+                                   uint32_t flags, void *hip_stream);
+/* out[i] = 1 / in[i]; an element = 0 (mod r) gives 0 and leaves its neighbours alone (arkworks' batch_inversion).  d_out may be d_in.  With
+ * MSM_NTT_IN_MONT | MSM_NTT_OUT_MONT x * 2^256 maps to x^-1 * 2^256.  One field inversion per inv_group elements. */
+int32_t msm_bn254_fr_batch_inverse_device(msm_ctx *ctx, const void *d_in, void *d_out, size_t n, uint32_t flags, void *hip_stream);
+/* host pointers, blocking; out == in allowed; stages through a device allocation of n * 32 bytes that is freed before the call returns */
+int32_t msm_bn254_fr_batch_inverse(msm_ctx *ctx, const uint32_t *in, uint32_t *out, size_t n, uint32_t flags);
+/* out[i] = L_i(tau) = Z(tau) w^i / (n (tau - w^i)), i < n = 2^log_n, Z(tau) = tau^n - 1, w = msm_bn254_fr_root_of_unity(log_n).  tau in the
+ * domain gives the unit vector (1 where w^i = tau).  log_n == 0: out[0] = 1.  log_n > 28: MSM_ERR_BAD_ARG.  flags: MSM_NTT_OUT_MONT only. */
+int32_t msm_bn254_fr_lagrange_device(msm_ctx *ctx, const uint32_t *tau_std, uint32_t log_n, void *d_out, uint32_t flags, void *hip_stream);
+/* out[i] = ka * a[i] + kb * b[i] + kc * c[i].  d_b / d_c NULL: the term is dropped; a NULL coefficient is 1.  d_out may alias any input. */
+int32_t msm_bn254_fr_lincomb_device(msm_ctx *ctx, const void *d_a, const uint32_t *ka_std, const void *d_b, const uint32_t *kb_std,
+                                    const void *d_c, const uint32_t *kc_std, void *d_out, size_t n, uint32_t flags, void *hip_stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 /* the plan of a call on n points under (window_bits, flags); with MSM_FLAG_WINDOW_TABLE in flags: the plan of a RESIDENT call on a
  * set of n bases uploaded under those flags (window width, table factor, table memory) */

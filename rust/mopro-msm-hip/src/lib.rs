@@ -229,6 +229,38 @@ extern "C" {
     ) -> i32;
 }
 
+/// msm_fr_vector_plan_t: the inversion group and the elements a workgroup covers in the scalar-vector calls
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmFrVectorPlan {
+    pub inv_group: u32,
+    pub block_points: u32,
+    pub powers_block_points: u32,
+    pub reserved: u32,
+}
+
+// The scalars of a setup made in HBM (include/msm_hip.h): powers, inverses, Lagrange coefficients, linear combinations --
+// what the fixed-base calls read as k_i.  tau, base, scale and the coefficients are host pointers to 8 standard-form words.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_fr_vector_plan(out: *mut MsmFrVectorPlan) -> i32;
+    pub fn msm_bn254_fr_powers_device(
+        ctx: *mut MsmCtx, base_std: *const u32, scale_std: *const u32, first: u64, d_out: *mut core::ffi::c_void, n: usize, flags: u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_batch_inverse_device(
+        ctx: *mut MsmCtx, d_in: *const core::ffi::c_void, d_out: *mut core::ffi::c_void, n: usize, flags: u32, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_batch_inverse(ctx: *mut MsmCtx, input: *const u32, out: *mut u32, n: usize, flags: u32) -> i32;
+    pub fn msm_bn254_fr_lagrange_device(
+        ctx: *mut MsmCtx, tau_std: *const u32, log_n: u32, d_out: *mut core::ffi::c_void, flags: u32, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_lincomb_device(
+        ctx: *mut MsmCtx, d_a: *const core::ffi::c_void, ka_std: *const u32, d_b: *const core::ffi::c_void, kb_std: *const u32,
+        d_c: *const core::ffi::c_void, kc_std: *const u32, d_out: *mut core::ffi::c_void, n: usize, flags: u32, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 
