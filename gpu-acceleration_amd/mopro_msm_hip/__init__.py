@@ -28,6 +28,7 @@ NTT_INVERSE, NTT_IN_MONT, NTT_OUT_MONT = 1, 2, 4  # MSM_NTT_*: inverse transform
 R1CS_COEF_STD, R1CS_COEF_MONT, R1CS_COEF_MONT2 = 0, 1, 2  # MSM_R1CS_COEF_*: a coefficient's words are c / c * 2^256 (arkworks Fr.0) / c * 2^512 (a snarkjs zkey's section 4)
 R1CS_C_FROM_AB = 8  # MSM_R1CS_C_FROM_AB: the eval writes c[i] = a[i] * b[i] instead of (matrix 2) * w
 FB_OUT_STD = 8  # MSM_FB_OUT_STD: the fixed-base products come out in standard form (default: arkworks Montgomery words); NTT_IN_MONT is honoured too
+PM_BASES_STD = 16  # MSM_PM_BASES_STD: the bases of the element-wise multiplication are standard-form integers (default: arkworks Montgomery words)
 G2_CHECK_CURVE, G2_CHECK_SUBGROUP = 1, 2  # MSM_G2_CHECK_*: coordinates < p and on the twist / [r]P = O (implies the curve check)
 OK, ERR_EMPTY, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE, ERR_INVALID_DATA = 0, -1, -2, -3, -4, -5, -6, -7
 
@@ -50,6 +51,7 @@ ABI_SYMBOLS = [
     "msm_bn254_g2_fixed_base_plan", "msm_bn254_g2_fixed_base_mul_device", "msm_bn254_g2_fixed_base_mul",
     "msm_bn254_fr_vector_plan", "msm_bn254_fr_powers_device", "msm_bn254_fr_batch_inverse_device", "msm_bn254_fr_batch_inverse",
     "msm_bn254_fr_lagrange_device", "msm_bn254_fr_lincomb_device",
+    "msm_bn254_g1_pointwise_mul_plan", "msm_bn254_g1_pointwise_mul_device", "msm_bn254_g1_scale_device", "msm_bn254_g1_pointwise_mul",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -121,6 +123,14 @@ class FixedBaseG2Plan(C.Structure):
 class FrVectorPlan(C.Structure):
     """msm_fr_vector_plan_t: the inversion group and the elements a workgroup covers in the scalar-vector calls"""
     _fields_ = [("inv_group", C.c_uint32), ("block_points", C.c_uint32), ("powers_block_points", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class PointwisePlan(C.Structure):
+    """msm_pointwise_plan_t: the inversion group, the ladder's positions and the points a lane keeps of an element-wise multiplication"""
+    _fields_ = [("inv_group", C.c_uint32), ("ladder_bits", C.c_uint32), ("table_points", C.c_uint32), ("reserved", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -219,6 +229,10 @@ def bind_product_abi(L):
     L.msm_bn254_g2_fixed_base_plan.argtypes = [C.c_uint32, C.POINTER(FixedBaseG2Plan)]
     L.msm_bn254_g2_fixed_base_mul_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.msm_bn254_g2_fixed_base_mul.argtypes = [vp, _u32p, C.c_uint32, _u32p, C.c_size_t, C.c_uint32, C.c_uint32, _u32p, _u8p]
+    L.msm_bn254_g1_pointwise_mul_plan.argtypes = [C.POINTER(PointwisePlan)]
+    L.msm_bn254_g1_pointwise_mul_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+    L.msm_bn254_g1_scale_device.argtypes = [vp, vp, vp, _u32p, C.c_size_t, C.c_uint32, vp, vp, vp]
+    L.msm_bn254_g1_pointwise_mul.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, C.c_uint32, _u32p, _u8p]
     L.msm_bn254_fr_vector_plan.argtypes = [C.POINTER(FrVectorPlan)]
     L.msm_bn254_fr_powers_device.argtypes = [vp, _u32p, _u32p, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp]
     L.msm_bn254_fr_batch_inverse_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
@@ -404,6 +418,17 @@ def fixed_base_plan(window_bits=0):
     rc = lib.msm_bn254_g1_fixed_base_plan(window_bits, C.byref(p))
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g1_fixed_base_plan failed ({rc})")
+    return p.as_dict()
+
+
+def pointwise_mul_plan():
+    """the inversion group, the positions of the ladder and the points a lane keeps in registers in the element-wise multiplication, as a dict of
+    msm_pointwise_plan_t (host only: no context, no GPU)"""
+    p = PointwisePlan()
+    lib = load_library()
+    rc = lib.msm_bn254_g1_pointwise_mul_plan(C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g1_pointwise_mul_plan failed ({rc})")
     return p.as_dict()
 
 
@@ -834,6 +859,37 @@ class MsmContext:
         b = _words(base, 32)
         self._check(self._lib.msm_bn254_g2_fixed_base_mul_device(self._h, _p32(b), form, d_scalars, n, window_bits, flags, d_out_xy, d_out_inf,
                                                                  stream))
+
+    # -- BN254 G1 element-wise: out[i] = k_i * P_i, n points each with its own scalar (or all with one): the update of an existing setup ---
+    def pointwise_mul(self, bases, scalars, form=FORM_STD, inf=None, flags=0):
+        """host arrays: n x 16 base words (x, y in `form`), n x 8 scalar words (any 256-bit patterns; flags NTT_IN_MONT: arkworks Fr.0 words) and
+        optionally n infinity bytes -> (n x 16 words xy, n bytes inf); the coordinates are arkworks Montgomery words, standard form with
+        FB_OUT_STD.  The bases are not validated (validate_g1 does that)"""
+        b, k = _words(bases, 16), _words(scalars, 8)
+        if b.shape[0] != k.shape[0]:
+            raise MsmError(ERR_BAD_ARG, "as many scalars as bases")
+        xy, out_inf = np.zeros((k.shape[0], 16), np.uint32), np.zeros(k.shape[0], np.uint8)
+        inf, inf_p = self._inf_ptr(inf)
+        if inf is not None and inf.size != k.shape[0]:
+            raise MsmError(ERR_BAD_ARG, "as many infinity bytes as bases")
+        self._check(self._lib.msm_bn254_g1_pointwise_mul(self._h, _p32(b), form, inf_p, _p32(k), k.shape[0], flags, _p32(xy),
+                                                         out_inf.ctypes.data_as(_u8p)))
+        return xy, out_inf
+
+    def pointwise_mul_device(self, d_bases, d_scalars, n, d_out_xy, d_out_inf, d_inf=None, flags=0, stream=None):
+        """raw device pointers: n x 16 base words, n x 8 scalar words and optionally n infinity bytes in, n x 16 words xy and n bytes inf out;
+        d_out_xy may be d_bases and d_out_inf may be d_inf (in place); flags NTT_IN_MONT / FB_OUT_STD / PM_BASES_STD; enqueued on `stream`
+        (None: the context's); nothing is kept on the context"""
+        self._check(self._lib.msm_bn254_g1_pointwise_mul_device(self._h, d_bases, d_inf, d_scalars, n, flags, d_out_xy, d_out_inf, stream))
+
+    def scale_device(self, d_bases, k, n, d_out_xy, d_out_inf, d_inf=None, flags=0, stream=None):
+        """out[i] = k * P_i for ONE scalar k (an int or 8 standard-form words, read modulo r) on raw device pointers; flags FB_OUT_STD /
+        PM_BASES_STD; otherwise as pointwise_mul_device"""
+        self._check(self._lib.msm_bn254_g1_scale_device(self._h, d_bases, d_inf, _p32(_fr_words(k)), n, flags, d_out_xy, d_out_inf, stream))
+
+    @staticmethod
+    def pointwise_mul_plan():
+        return pointwise_mul_plan()
 
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))
