@@ -6,9 +6,11 @@
 // R == 0 is only tested on that cold path.
 //
 // Value bounds (multiples of p per component; fp2_bn254.hpp gives the product rules; k = 0.0059):
-//   affine operand   x < 1 (canonical), y < 2 (y or the negation 2p - y)
+//   affine operand   x < 1 (canonical), y <= 2 (y or the negation 2p - y: exactly 2p for a zero component of y, which fp2_neg<2> does not reduce)
 //   XYZZ everywhere  X < 12, Y < 8, ZZ < 4.2, ZZZ < 4.2  -- every function below re-establishes these
-// Every fp2_mul<K>(a, b) needs b.c1 < (K-1)p, every fp2_sub<K>(a, b) b < (K-1)p; the bounds are written at each call.
+// Every fp2_mul<K>(a, b) needs b.c1 < (K-1)p, every fp2_sub<K>(a, b) b < (K-1)p; the bounds are written at each call.  (The rule is sufficient, not
+// tight: a K*p pad takes a subtrahend limb by limb up to about K*p - 2^232, so only an operand within 3e-7 p of the top of its range can tell a pad
+// that is one p too small -- tools/g2_bounds_check.cpp puts operands there.)
 #pragma once
 #include "fp2_bn254.hpp"
 

@@ -114,6 +114,39 @@ int32_t msm_test_g2_sqrt(msm_ctx* c, const uint32_t* a_std, const uint8_t* want_
     HIPCHK(c, hipMemcpy(ok, tok.p, n, hipMemcpyDeviceToHost));
     return MSM_OK;
 }
+// the G2 group law on raw limb records (msmk::k_test_g2): alloc / copy / launch / sync as run_test_kernel
+int32_t msm_test_g2_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+    if (!c || !a || !out) return MSM_ERR_BAD_ARG;
+    if (op > MSM_OP_G2_DBL) return fail(c, MSM_ERR_BAD_ARG, "unknown G2 op %u", op);
+    if (op != MSM_OP_G2_DBL && !b) return MSM_ERR_BAD_ARG;
+    if (n == 0) return MSM_ERR_EMPTY;
+    if (n > 0x7FFFFFFFull / msmk::XW2) return fail(c, MSM_ERR_BAD_ARG, "n too large");
+    const size_t a_words = msmk::XW2, b_words = op == MSM_OP_G2_MADD ? 36 : op == MSM_OP_G2_ADD ? (size_t)msmk::XW2 : 0;
+    // a limb of 2^29 or more could overflow a column accumulator of the multiplication: a malformed test is refused, not run
+    for (size_t i = 0; i < n * a_words; i++)
+        if (a[i] > bn254::FP_MASK) return fail(c, MSM_ERR_BAD_ARG, "a: word %zu of record %zu is not a 29-bit limb", i % a_words, i / a_words);
+    for (size_t i = 0; i < n * b_words; i++)
+        if (b[i] > bn254::FP_MASK) return fail(c, MSM_ERR_BAD_ARG, "b: word %zu of record %zu is not a 29-bit limb", i % b_words, i / b_words);
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    DevTmp ta, tb_, tout;  // freed on every exit path
+    HIPCHK(c, hipMalloc(&ta.p, n * a_words * 4));
+    HIPCHK(c, hipMalloc(&tout.p, n * a_words * 4));
+    HIPCHK(c, hipMemcpy(ta.p, a, n * a_words * 4, hipMemcpyHostToDevice));
+    if (b_words) {
+        HIPCHK(c, hipMalloc(&tb_.p, n * b_words * 4));
+        HIPCHK(c, hipMemcpy(tb_.p, b, n * b_words * 4, hipMemcpyHostToDevice));
+    }
+    const uint32_t *da = (const uint32_t*)ta.p, *db = (const uint32_t*)tb_.p;
+    uint32_t* dout = (uint32_t*)tout.p;
+    if (op == MSM_OP_G2_MADD) msmk::k_test_g2<MSM_OP_G2_MADD><<<grid1(n, 64), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n);
+    else if (op == MSM_OP_G2_ADD) msmk::k_test_g2<MSM_OP_G2_ADD><<<grid1(n, 64), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n);
+    else msmk::k_test_g2<MSM_OP_G2_DBL><<<grid1(n, 64), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(out, dout, n * a_words * 4, hipMemcpyDeviceToHost));
+    return MSM_OK;
+}
 int32_t msm_calibrate(msm_ctx* c, double* mad_per_s, double* fp_mul_per_s) {
     if (!c) return MSM_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->mu);

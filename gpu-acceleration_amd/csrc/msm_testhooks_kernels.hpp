@@ -5,6 +5,7 @@
 //   the integer-multiplier calibration kernels and the XYZZ -> Jacobian dump of the stage tests.
 #pragma once
 #include "msm_kernels.hpp"
+#include "msm_kernels_g2.hpp"
 
 namespace msmk {
 
@@ -272,6 +273,29 @@ __global__ void k_dump_xyzz_as_jacobian(const uint32_t* __restrict__ recs, uint3
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     store_jacobian_mont256(out + (size_t)i * 24, xyzz_to_jacobian(load_xyzz(recs + (size_t)i * XW)));
+}
+
+// G2 group law on RAW limb records (msm_test_g2_op): one lane per element loads what the caller wrote -- 72 words X.c0 X.c1 Y.c0 Y.c1 ZZ.c0 ZZ.c1
+// ZZZ.c0 ZZZ.c1 (b of the mixed addition: 36 words x.c0 x.c1 y.c0 y.c1), 9 limbs of 29 bits each, internal domain, ANY representative within the
+// bounds of ec_g2_bn254.hpp -- calls the one function and stores the limbs it got.  No conversion, no reduction: the test chooses the
+// representative the device works on and reads back the one it produced.  One kernel per operation (one inlined group operation each).
+// OP: 0 xyzz2_madd, 1 xyzz2_add, 2 xyzz2_dbl (MSM_OP_G2_* of include/msm_hip_testhooks.h)
+template <uint32_t OP>
+__global__ void __launch_bounds__(64) k_test_g2(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    xyzz2 r = load_xyzz2(a + (size_t)i * XW2);
+    if (OP == 0) {
+        const uint32_t* bp = b + (size_t)i * 36;
+        affine2 q;
+        load_fp9(q.x.c0, bp), load_fp9(q.x.c1, bp + 9), load_fp9(q.y.c0, bp + 18), load_fp9(q.y.c1, bp + 27);
+        xyzz2_madd(r, q);
+    } else if (OP == 1) {
+        r = xyzz2_add(r, load_xyzz2(b + (size_t)i * XW2));
+    } else {
+        r = xyzz2_dbl(r);
+    }
+    store_xyzz2(out + (size_t)i * XW2, r);
 }
 
 }  // namespace msmk

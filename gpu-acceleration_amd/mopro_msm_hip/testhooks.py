@@ -18,8 +18,9 @@ HOOK_SYMBOLS = [
     "msm_bn254_g1_generate_device", "msm_bn254_generate_scalars_host", "msm_test_fp_op", "msm_test_g1_op",
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
-    "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2",
+    "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2", "msm_test_g2_op",
 ]
+OP_G2_MADD, OP_G2_ADD, OP_G2_DBL = 0, 1, 2  # MSM_OP_G2_* of include/msm_hip_testhooks.h
 _lib = None
 
 
@@ -42,6 +43,7 @@ def load_hooks_library():
     L.msm_test_fp_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_g1_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_g2_sqrt.argtypes = [vp, _u32p, _u8p, _u32p, _u8p, C.c_size_t]
+    L.msm_test_g2_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_decompose.argtypes = [vp, _u32p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32)]
     L.msm_test_abandon_after_sort.argtypes = [vp, _u32p, C.c_size_t]
     L.msm_calibrate.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -101,6 +103,25 @@ class HooksContext(MsmContext):
         out, ok = np.zeros_like(a), np.zeros(a.shape[0], np.uint8)
         self._check(self._lib.msm_test_g2_sqrt(self._h, _p32(a), want.ctypes.data_as(_u8p), _p32(out), ok.ctypes.data_as(_u8p), a.shape[0]))
         return out, ok
+
+    def test_g2_op(self, op, a, b=None):
+        """the G2 group law on raw limb records (msm_test_g2_op): a n x 72 limbs (XYZZ over Fq2, 9 x 29-bit limbs per component, internal domain, any
+        representative within the bounds of ec_g2_bn254.hpp), b n x 36 (OP_G2_MADD: affine), n x 72 (OP_G2_ADD) or None (OP_G2_DBL) -> n x 72 limbs,
+        exactly what the device stored"""
+        if op not in (OP_G2_MADD, OP_G2_ADD, OP_G2_DBL):
+            raise ValueError(f"unknown G2 op {op}")
+        a = _words(a, 72)
+        if op == OP_G2_DBL:
+            b = None
+        else:  # the C hook reads n records of b: a missing or shorter b must not reach it
+            if b is None:
+                raise ValueError("OP_G2_MADD / OP_G2_ADD need b")
+            b = _words(b, 36 if op == OP_G2_MADD else 72)
+            if b.shape[0] != a.shape[0]:
+                raise ValueError(f"a holds {a.shape[0]} records, b {b.shape[0]}")
+        out = np.zeros_like(a)
+        self._check(self._lib.msm_test_g2_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
+        return out
 
     def ntt_set_tile_log2(self, tile_log2):
         """the LDS tile (log2 elements) of the transforms that follow on this context: 4 or 10; 0 = the plan's own"""

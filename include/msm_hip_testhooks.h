@@ -43,6 +43,16 @@ int32_t msm_test_g1_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint3
  * want_larger: n bytes (non-zero: the root that is the larger of (y, -y), see msm_bn254_g2_compress); out_std: n x 16 standard-form words of the
  * root (zero when there is none); ok: n bytes, 1 = a is a square. */
 int32_t msm_test_g2_sqrt(msm_ctx *ctx, const uint32_t *a_std, const uint8_t *want_larger, uint32_t *out_std, uint8_t *ok, size_t n);
+/* the G2 group law of csrc/ec_g2_bn254.hpp on RAW limb records: n elements, one device lane each, no conversion and no reduction on the way in or
+ * out.  A record is 9 limbs of 29 bits per Fq component (one u32 word per limb, least significant first; value = sum limb_i * 2^(29 i)), internal
+ * Montgomery domain (x * 2^261 mod p, plus any multiple of p the bounds of ec_g2_bn254.hpp allow: X < 12p, Y < 8p, ZZ, ZZZ < 4.2p; affine x < p,
+ * y < 2p).  XYZZ record: X.c0 X.c1 Y.c0 Y.c1 ZZ.c0 ZZ.c1 ZZZ.c0 ZZZ.c1 (72 words); affine record: x.c0 x.c1 y.c0 y.c1 (36 words).  The identity is
+ * ZZ == 0 with every limb zero.  The caller picks the representative the device computes on and reads back exactly the limbs it produced.
+ * An input limb >= 2^29 is MSM_ERR_BAD_ARG (the bounds above are the caller's to keep: the device asserts nothing). */
+#define MSM_OP_G2_MADD 0u /* a: XYZZ record (72) + b: affine record (36) -> XYZZ record (72) */
+#define MSM_OP_G2_ADD 1u  /* a: 72 + b: 72 -> 72 */
+#define MSM_OP_G2_DBL 2u  /* a: 72 -> 72 */
+int32_t msm_test_g2_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
 /* signed/unsigned digit decomposition of the planner's choice, digits[w*n + i] as int32 */
 int32_t msm_test_decompose(msm_ctx *ctx, const uint32_t *scalars, size_t n, uint32_t window_bits, int32_t *digits);
 
