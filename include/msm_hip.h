@@ -584,6 +584,43 @@ int32_t msm_bn254_g1_scale_device(msm_ctx *ctx, const void *d_bases_xy, const vo
 int32_t msm_bn254_g1_pointwise_mul(msm_ctx *ctx, const uint32_t *bases_xy, uint32_t base_form, const uint8_t *inf_mask, const uint32_t *scalars,
                                    size_t n, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
 
+/* ---- BN254 G1 group transform (ABI 7): the discrete Fourier transform over G1 POINTS, in place, natural order in and out,
+ *      with the domain and the direction conventions of msm_bn254_fr_ntt_device:
+ *          forward:  out[j] = sum_i w^(ij) * in[i];     with MSM_NTT_INVERSE:  out[i] = n^-1 * sum_j w^(-ij) * in[j]
+ *      w = msm_bn254_fr_root_of_unity(log_n), n = 2^log_n.  The inverse turns a powers-of-tau output tauG1[j] = tau^j * G into the Lagrange basis
+ *      L_i(tau) * G without anybody knowing tau (snarkjs "powersoftau prepare phase2", halo2's g_lagrange); with tau in hand
+ *      msm_bn254_fr_lagrange_device and the fixed-base call are the cheaper route.  (n / 2) * log_n scalar multiplications of points: a
+ *      bit-reversal sweep, then log_n radix-2 stages of one lane per butterfly, each the ladder of the element-wise multiplication above, two
+ *      complete additions and one normalisation; the first stage (every twiddle 1) runs no ladder.
+ *      d_xy: batch contiguous arrays of n x 16 words, the (x, y) records of msm_bn254_g1_pointwise_mul_device; d_inf: batch * n bytes (nonzero =
+ *      the point at infinity, its words ignored), REQUIRED: an output can be the identity where no input was.  Both device memory, 16-byte
+ *      aligned, read and written.  flags: MSM_NTT_INVERSE (1u), MSM_PM_BASES_STD (16u; the input coordinates are standard-form integers),
+ *      MSM_FB_OUT_STD (8u; standard-form output); any other bit is MSM_ERR_BAD_ARG.  Outputs: canonical coordinates, word-exact; the identity is
+ *      inf = 1 with sixteen zero words, every other place has inf = 0.  Inputs are NOT validated: words that are no curve point give meaningless
+ *      points, never a fault -- the kernels make no data-dependent memory access.  log_n == 0 only converts the form and canonicalises the flag.
+ *      Stream-ordered on hip_stream (NULL = the context's stream): the call returns when enqueued.  Kept on the context, per log_n >= 2: the
+ *      n / 2 powers of w in standard form (msm_g1_fft_plan_t.table_bytes; one table serves both directions), built on the call's stream by its
+ *      first use.  A call on ANOTHER stream waits for the event behind that build, so calls of a context on two streams that first build a
+ *      table order themselves; afterwards they do not wait for each other, and the caller orders calls that share an array.
+ *      A coset form is not offered: multiply by g^i with msm_bn254_g1_pointwise_mul_device.  There is no G2 sibling.
+ *      Errors: a NULL or misaligned pointer, an unknown flag bit, log_n > 28, batch * n > 2^36, a bad base_form: MSM_ERR_BAD_ARG; batch == 0:
+ *      MSM_ERR_EMPTY; allocation failure: MSM_ERR_OOM.  A failed call writes nothing and the context stays usable. ---- */
+typedef struct {
+    uint16_t stages;         /* butterfly launches per 2^30 butterflies: log_n */
+    uint16_t ladder_stages;  /* ... of them with a scalar multiplication per butterfly: log_n - 1 (0 for log_n == 0) */
+    uint32_t inv_group;      /* butterflies that share one field inversion (twice per ladder stage: the slopes, the 2 * inv_group outputs) */
+    uint64_t table_bytes;    /* kept on the context for this size: n / 2 twiddles of 32 bytes (0 below log_n = 2) */
+} msm_g1_fft_plan_t;
+
+/* host only, no context */
+int32_t msm_bn254_g1_fft_plan(uint32_t log_n, msm_g1_fft_plan_t *out);
+int32_t msm_bn254_g1_fft_device(msm_ctx *ctx, void *d_xy, void *d_inf, uint32_t log_n, size_t batch, uint32_t flags, void *hip_stream);
+/* on host pointers, blocking.  base_form: MSM_FORM_STD / _MONT (MSM_PM_BASES_STD is not taken here); inf NULL: nothing is flagged; out_xy may be
+ * xy and out_inf may be inf.  The whole batch is staged in device memory (65 bytes per point, kept on the context): a transform cannot be
+ * chunked.  Pageable memory is pinned in place like every host-pointer call. */
+int32_t msm_bn254_g1_fft(msm_ctx *ctx, const uint32_t *xy, uint32_t base_form, const uint8_t *inf, uint32_t log_n, size_t batch, uint32_t flags,
+                         uint32_t *out_xy, uint8_t *out_inf);
+
 /* ---- BN254 scalar field Fr: the scalars of a setup made in HBM (ABI 7) -- what the fixed-base calls above read as k_i:
  *      powers of tau (the H query, KZG), element-wise inverses, the Lagrange coefficients L_i(tau) of the transforms' domain, and the linear
  *      combination of the L query.  Conventions of msm_bn254_fr_ntt_device: elements are 8 little-endian words; any 256-bit input pattern is

@@ -290,6 +290,31 @@ extern "C" {
     ) -> i32;
 }
 
+/// msm_g1_fft_plan_t: the stages of a G1 group transform, those that run a ladder, the inversion group, the bytes of the twiddle table
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmG1FftPlan {
+    pub stages: u16,
+    pub ladder_stages: u16,
+    pub inv_group: u32,
+    pub table_bytes: u64,
+}
+
+// The discrete Fourier transform over G1 points, in place in HBM (include/msm_hip.h "G1 group transform"): the inverse turns
+// tau^j * G into the Lagrange basis L_i(tau) * G without tau.  The points are not validated.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_g1_fft_plan(log_n: u32, out: *mut MsmG1FftPlan) -> i32;
+    pub fn msm_bn254_g1_fft_device(
+        ctx: *mut MsmCtx, d_xy: *mut core::ffi::c_void, d_inf: *mut core::ffi::c_void, log_n: u32, batch: usize, flags: u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_g1_fft(
+        ctx: *mut MsmCtx, xy: *const u32, base_form: u32, inf: *const u8, log_n: u32, batch: usize, flags: u32, out_xy: *mut u32,
+        out_inf: *mut u8,
+    ) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 
