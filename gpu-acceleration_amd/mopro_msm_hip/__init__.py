@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "msm_bn254_fr_lagrange_device", "msm_bn254_fr_lincomb_device",
     "msm_bn254_g1_pointwise_mul_plan", "msm_bn254_g1_pointwise_mul_device", "msm_bn254_g1_scale_device", "msm_bn254_g1_pointwise_mul",
     "msm_bn254_g1_fft_plan", "msm_bn254_g1_fft_device", "msm_bn254_g1_fft",
+    "msm_bn254_g2_pointwise_mul_plan", "msm_bn254_g2_pointwise_mul_device", "msm_bn254_g2_scale_device", "msm_bn254_g2_pointwise_mul",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -131,6 +132,14 @@ class FrVectorPlan(C.Structure):
 
 class PointwisePlan(C.Structure):
     """msm_pointwise_plan_t: the inversion group, the ladder's positions and the points a lane keeps of an element-wise multiplication"""
+    _fields_ = [("inv_group", C.c_uint32), ("ladder_bits", C.c_uint32), ("table_points", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class G2PointwisePlan(C.Structure):
+    """msm_pointwise_g2_plan_t: the same three figures for the G2 element-wise multiplication"""
     _fields_ = [("inv_group", C.c_uint32), ("ladder_bits", C.c_uint32), ("table_points", C.c_uint32), ("reserved", C.c_uint32)]
 
     def as_dict(self):
@@ -242,6 +251,10 @@ def bind_product_abi(L):
     L.msm_bn254_g1_pointwise_mul_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
     L.msm_bn254_g1_scale_device.argtypes = [vp, vp, vp, _u32p, C.c_size_t, C.c_uint32, vp, vp, vp]
     L.msm_bn254_g1_pointwise_mul.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, C.c_uint32, _u32p, _u8p]
+    L.msm_bn254_g2_pointwise_mul_plan.argtypes = [C.POINTER(G2PointwisePlan)]
+    L.msm_bn254_g2_pointwise_mul_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+    L.msm_bn254_g2_scale_device.argtypes = [vp, vp, vp, _u32p, C.c_size_t, C.c_uint32, vp, vp, vp]
+    L.msm_bn254_g2_pointwise_mul.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, C.c_uint32, _u32p, _u8p]
     L.msm_bn254_g1_fft_plan.argtypes = [C.c_uint32, C.POINTER(G1FftPlan)]
     L.msm_bn254_g1_fft_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_size_t, C.c_uint32, vp]
     L.msm_bn254_g1_fft.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_uint32, C.c_size_t, C.c_uint32, _u32p, _u8p]
@@ -441,6 +454,16 @@ def pointwise_mul_plan():
     rc = lib.msm_bn254_g1_pointwise_mul_plan(C.byref(p))
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g1_pointwise_mul_plan failed ({rc})")
+    return p.as_dict()
+
+
+def g2_pointwise_mul_plan():
+    """the same for the G2 element-wise multiplication, as a dict of msm_pointwise_g2_plan_t (host only: no context, no GPU)"""
+    p = G2PointwisePlan()
+    lib = load_library()
+    rc = lib.msm_bn254_g2_pointwise_mul_plan(C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g2_pointwise_mul_plan failed ({rc})")
     return p.as_dict()
 
 
@@ -913,6 +936,37 @@ class MsmContext:
     @staticmethod
     def pointwise_mul_plan():
         return pointwise_mul_plan()
+
+    # -- BN254 G2 element-wise: out[i] = k_i * Q_i on records of 32 words (x.c0, x.c1, y.c0, y.c1): the G2 half of a ceremony update ---------
+    def g2_pointwise_mul(self, bases, scalars, form=FORM_STD, inf=None, flags=0):
+        """host arrays: n x 32 base words (in `form`), n x 8 scalar words (any 256-bit patterns; flags NTT_IN_MONT: arkworks Fr.0 words) and
+        optionally n infinity bytes -> (n x 32 words xy, n bytes inf); the components are arkworks Montgomery words, standard form with
+        FB_OUT_STD.  The bases must be points of G2 and are not validated (validate_g2 with G2_CHECK_SUBGROUP does that)"""
+        b, k = _words(bases, 32), _words(scalars, 8)
+        if b.shape[0] != k.shape[0]:
+            raise MsmError(ERR_BAD_ARG, "as many scalars as bases")
+        xy, out_inf = np.zeros((k.shape[0], 32), np.uint32), np.zeros(k.shape[0], np.uint8)
+        inf, inf_p = self._inf_ptr(inf)
+        if inf is not None and inf.size != k.shape[0]:
+            raise MsmError(ERR_BAD_ARG, "as many infinity bytes as bases")
+        self._check(self._lib.msm_bn254_g2_pointwise_mul(self._h, _p32(b), form, inf_p, _p32(k), k.shape[0], flags, _p32(xy),
+                                                         out_inf.ctypes.data_as(_u8p)))
+        return xy, out_inf
+
+    def g2_pointwise_mul_device(self, d_bases, d_scalars, n, d_out_xy, d_out_inf, d_inf=None, flags=0, stream=None):
+        """raw device pointers: n x 32 base words, n x 8 scalar words and optionally n infinity bytes in, n x 32 words xy and n bytes inf out;
+        d_out_xy may be d_bases and d_out_inf may be d_inf (in place); flags NTT_IN_MONT / FB_OUT_STD / PM_BASES_STD; enqueued on `stream`
+        (None: the context's); nothing is kept on the context"""
+        self._check(self._lib.msm_bn254_g2_pointwise_mul_device(self._h, d_bases, d_inf, d_scalars, n, flags, d_out_xy, d_out_inf, stream))
+
+    def g2_scale_device(self, d_bases, k, n, d_out_xy, d_out_inf, d_inf=None, flags=0, stream=None):
+        """out[i] = k * Q_i for ONE scalar k (an int or 8 standard-form words, read modulo r) on raw device pointers; flags FB_OUT_STD /
+        PM_BASES_STD; otherwise as g2_pointwise_mul_device"""
+        self._check(self._lib.msm_bn254_g2_scale_device(self._h, d_bases, d_inf, _p32(_fr_words(k)), n, flags, d_out_xy, d_out_inf, stream))
+
+    @staticmethod
+    def g2_pointwise_mul_plan():
+        return g2_pointwise_mul_plan()
 
     # -- BN254 G1 group transform: the DFT over points, in place; the inverse makes the Lagrange basis L_i(tau) * G from tau^j * G --------------
     def g1_fft(self, xy, log_n, form=FORM_STD, inf=None, batch=1, flags=0, out_xy=None, out_inf=None):

@@ -621,6 +621,51 @@ int32_t msm_bn254_g1_fft_device(msm_ctx *ctx, void *d_xy, void *d_inf, uint32_t 
 int32_t msm_bn254_g1_fft(msm_ctx *ctx, const uint32_t *xy, uint32_t base_form, const uint8_t *inf, uint32_t log_n, size_t batch, uint32_t flags,
                          uint32_t *out_xy, uint8_t *out_inf);
 
+/* ---- BN254 G2 element-wise scalar multiplication (ABI 7): out[i] = k_i * Q_i on G2 records -- the other half of a ceremony
+ *      update: the tauG2 section (tauG2[i] <- tau'^i * tauG2[i]) and betaG2 of a powers-of-tau contribution, deltaG2 of a Groth16 phase-2
+ *      contribution, a re-randomised G2 base set.  Where the points share one base, msm_bn254_g2_fixed_base_mul_device is the call to use.
+ *      The contract is that of the G1 element-wise calls above, word for word, wherever it applies.  Records: a point is 32 words, x.c0, x.c1,
+ *      y.c0, y.c1 -- what msm_bn254_g2_device takes as d_bases_mont and msm_bn254_g2_fixed_base_mul_device writes: arkworks Montgomery words,
+ *      standard-form integers with MSM_PM_BASES_STD -- and n bytes d_inf_mask (nonzero = the point at infinity, its words ignored) or NULL.
+ *      Scalars: 8 little-endian words, ANY 256-bit pattern, read modulo r; with MSM_NTT_IN_MONT the words are arkworks Fr.0.
+ *      THE BASES MUST BE POINTS OF G2, the subgroup of order r: the twist's cofactor is not 1, and reading a scalar modulo r is only right in
+ *      G2 -- and so is the endomorphism the kernel uses.  The call does NOT validate them; msm_bn254_g2_validate(_device) with
+ *      MSM_G2_CHECK_SUBGROUP does.  Anything else -- words that are no curve point, components of p or above, a point of the twist outside
+ *      G2 -- gives a meaningless point at its own place, never a fault and never a wrong neighbour: the kernel makes no data-dependent memory
+ *      access.  Outputs: canonical components, Montgomery words by default, standard form with MSM_FB_OUT_STD; out_inf[i] = 1 and all 32 words
+ *      zero for the identity (the base is flagged, or k_i = 0 mod r), out_inf[i] = 0 otherwise.
+ *      Aliasing: d_out_xy == d_bases_xy and d_out_inf == d_inf_mask are allowed (each on its own); any other overlap is the caller's error.
+ *      The device forms are stream-ordered on hip_stream (NULL = the context's stream), return when enqueued and keep NOTHING on the context --
+ *      no table, no scratch array, no event -- so two calls on two streams do not wait for each other, and the caller orders calls that share an
+ *      array.  One kernel per launch: the inv_group points of a workgroup share two field inversions (of the norms, in Fq); a call of any n is
+ *      cut into launches of at most 2^30 points.  The host-pointer form stages at most 2^19 points (161 bytes each: 85 MB of device memory,
+ *      kept on the context and released with it) at a time and pins pageable memory like every host-pointer call.
+ *      Errors, as for G1: a NULL pointer (d_inf_mask / inf_mask excepted) or a device array that is not 16-byte aligned, an unknown flag bit, a
+ *      bad base_form: MSM_ERR_BAD_ARG; n == 0: MSM_ERR_EMPTY; allocation failure: MSM_ERR_OOM.  The context stays usable after any, and a
+ *      failed call writes nothing. ---- */
+typedef struct {
+    uint32_t inv_group;    /* points that share one field inversion (twice per call: the table's slopes, the outputs) */
+    uint32_t ladder_bits;  /* positions of the joint double-and-add ladder: the bits of a half of the GLV split */
+    uint32_t table_points; /* affine points a lane works from: Q, lambda * Q and their sum, signs folded in */
+    uint32_t reserved;
+} msm_pointwise_g2_plan_t;
+
+/* host only, no context */
+int32_t msm_bn254_g2_pointwise_mul_plan(msm_pointwise_g2_plan_t *out);
+
+/* out[i] = k_i * Q_i.  d_bases_xy: n x 32 words; d_inf_mask: n bytes or NULL; d_scalars: n x 8 words; d_out_xy: n x 32 words; d_out_inf: n bytes --
+ * device memory, 16-byte aligned.  flags: MSM_NTT_IN_MONT, MSM_FB_OUT_STD, MSM_PM_BASES_STD. */
+int32_t msm_bn254_g2_pointwise_mul_device(msm_ctx *ctx, const void *d_bases_xy, const void *d_inf_mask, const void *d_scalars, size_t n,
+                                          uint32_t flags, void *d_out_xy, void *d_out_inf, void *hip_stream);
+/* out[i] = k * Q_i for ONE scalar.  k_std: HOST pointer to 8 standard-form words (any pattern, read modulo r); it is split on the host and
+ * travels with the launch, so every lane walks the same ladder.  flags: MSM_FB_OUT_STD, MSM_PM_BASES_STD; MSM_NTT_IN_MONT is MSM_ERR_BAD_ARG. */
+int32_t msm_bn254_g2_scale_device(msm_ctx *ctx, const void *d_bases_xy, const void *d_inf_mask, const uint32_t *k_std, size_t n, uint32_t flags,
+                                  void *d_out_xy, void *d_out_inf, void *hip_stream);
+/* the first one on host pointers, blocking.  base_form: MSM_FORM_STD / _MONT as in msm_bn254_g2 (MSM_PM_BASES_STD is not taken here);
+ * inf_mask NULL: no point is flagged; out_xy may be bases_xy and out_inf may be inf_mask. */
+int32_t msm_bn254_g2_pointwise_mul(msm_ctx *ctx, const uint32_t *bases_xy, uint32_t base_form, const uint8_t *inf_mask, const uint32_t *scalars,
+                                   size_t n, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
+
 /* ---- BN254 scalar field Fr: the scalars of a setup made in HBM (ABI 7) -- what the fixed-base calls above read as k_i:
  *      powers of tau (the H query, KZG), element-wise inverses, the Lagrange coefficients L_i(tau) of the transforms' domain, and the linear
  *      combination of the L query.  Conventions of msm_bn254_fr_ntt_device: elements are 8 little-endian words; any 256-bit input pattern is

@@ -315,6 +315,35 @@ extern "C" {
     ) -> i32;
 }
 
+/// msm_pointwise_g2_plan_t: the same three figures for the G2 element-wise multiplication
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmPointwiseG2Plan {
+    pub inv_group: u32,
+    pub ladder_bits: u32,
+    pub table_points: u32,
+    pub reserved: u32,
+}
+
+// out[i] = k_i * Q_i on G2 records of 32 words (include/msm_hip.h "G2 element-wise scalar multiplication"): the tauG2,
+// betaG2 and deltaG2 side of a ceremony update.  The bases must be points of G2 and are not validated.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_g2_pointwise_mul_plan(out: *mut MsmPointwiseG2Plan) -> i32;
+    pub fn msm_bn254_g2_pointwise_mul_device(
+        ctx: *mut MsmCtx, d_bases_xy: *const core::ffi::c_void, d_inf_mask: *const core::ffi::c_void, d_scalars: *const core::ffi::c_void, n: usize,
+        flags: u32, d_out_xy: *mut core::ffi::c_void, d_out_inf: *mut core::ffi::c_void, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_g2_scale_device(
+        ctx: *mut MsmCtx, d_bases_xy: *const core::ffi::c_void, d_inf_mask: *const core::ffi::c_void, k_std: *const u32, n: usize, flags: u32,
+        d_out_xy: *mut core::ffi::c_void, d_out_inf: *mut core::ffi::c_void, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_g2_pointwise_mul(
+        ctx: *mut MsmCtx, bases_xy: *const u32, base_form: u32, inf_mask: *const u8, scalars: *const u32, n: usize, flags: u32, out_xy: *mut u32,
+        out_inf: *mut u8,
+    ) -> i32;
+}
+
 struct Ctx(*mut MsmCtx);
 unsafe impl Send for Ctx {}
 

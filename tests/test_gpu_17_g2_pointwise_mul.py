@@ -1,0 +1,354 @@
+"""The G2 element-wise multiplication on the GPU (-m gpu): msm_bn254_g2_pointwise_mul(_device) and msm_bn254_g2_scale_device against a model
+built on the independent Python G2 law -- sizes around the inversion group, the edge scalars of the split and the ladder, identities at every
+place of a group, one scalar for all points, in place, the G2 points of a real proving key, input that is not in G2 between live neighbours,
+errors, two streams, the host form, and the two ceremony updates (the tauG2 section of a powers-of-tau contribution, deltaG2 of a phase-2
+contribution) end to end.  Inputs come from fixed seeds; every comparison is word-exact."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import mopro_msm_hip as mh
+from oracle import bn254_oracle as orc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import g2_pointwise_mul_cases as pm2  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+P, R = pm2.P, pm2.R
+g2, fb2 = pm2.g2, pm2.fb2
+IM, OS, BS = mh.NTT_IN_MONT, mh.FB_OUT_STD, mh.PM_BASES_STD
+FILL = 0x5A  # every byte of the outputs before a call: a record the kernel skips shows up
+G = 256      # the inversion group; test_sizes... checks it against the plan
+SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 513, 4096]
+NMAX = 4096
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = mh.MsmContext()
+    yield c
+    c.close()
+
+
+def dev(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.uint8).copy()).to("cuda:0")
+
+
+def outputs(n):
+    return dev(np.full((n, 32), FILL * 0x01010101, np.uint32)), dev(np.full(n, FILL, np.uint8))
+
+
+def host(d_xy, d_inf):
+    import torch
+    torch.cuda.synchronize()
+    return d_xy.cpu().numpy().view(np.uint32).reshape(-1, 32), d_inf.cpu().numpy().view(np.uint8)
+
+
+def device_mul(c, base_words, k_words, inf=None, flags=0, stream=None):
+    import torch
+    n = k_words.shape[0]
+    d_b, d_k = dev(base_words), dev(k_words)
+    d_m = None if inf is None else dev(np.asarray(inf, np.uint8))
+    d_xy, d_inf = outputs(n)
+    torch.cuda.synchronize()  # the arrays were made on torch's stream
+    c.g2_pointwise_mul_device(d_b.data_ptr(), d_k.data_ptr(), n, d_xy.data_ptr(), d_inf.data_ptr(), None if d_m is None else d_m.data_ptr(), flags, stream)
+    return host(d_xy, d_inf)
+
+
+def device_scale(c, base_words, k, inf=None, flags=0, stream=None):
+    import torch
+    n = base_words.shape[0]
+    d_b = dev(base_words)
+    d_m = None if inf is None else dev(np.asarray(inf, np.uint8))
+    d_xy, d_inf = outputs(n)
+    torch.cuda.synchronize()
+    c.g2_scale_device(d_b.data_ptr(), k, n, d_xy.data_ptr(), d_inf.data_ptr(), None if d_m is None else d_m.data_ptr(), flags, stream)
+    return host(d_xy, d_inf)
+
+
+def same(got, want, what=None):
+    (xy, inf), (wxy, winf) = got, want
+    assert xy.shape == wxy.shape and inf.shape == winf.shape, what
+    bad = np.flatnonzero((xy != wxy).any(axis=1) | (inf != winf))
+    assert bad.size == 0, (what, "first wrong point", int(bad[0]), "of", xy.shape[0], "wrong", int(bad.size))
+
+
+def cut(want, n):
+    return want[0][:n], want[1][:n]
+
+
+@pytest.fixture(scope="module")
+def ref():
+    """4096 seeded bases b_i * H in both forms, 4096 seeded 256-bit patterns, and what the call must give for them per flag set, computed once;
+    the tests take prefixes and leave it unchanged"""
+    ks, bs = pm2.patterns(0x9027F1, NMAX), pm2.logs(0x9027F2, NMAX)
+    inv_mont = pow(pm2.MONT_R, -1, R)
+    pts = pm2.base_points(bs)
+    mont = pm2.expected(ks, bs)
+    return {"ks": ks, "bs": bs, "k_words": pm2.to_words(ks), "mont": pm2.point_array(pts, pm2.FORM_MONT), "std": pm2.point_array(pts, pm2.FORM_STD),
+            "want": {0: mont, OS: pm2.expected(ks, bs, out_std=True), IM: pm2.expected([k * inv_mont % R for k in ks], bs), BS: mont}}
+
+
+# 1
+@pytest.mark.parametrize("flags", [0, OS, IM, BS])
+@pytest.mark.parametrize("n", SIZES)
+def test_sizes_around_the_inversion_group(ctx, ref, n, flags):
+    assert mh.g2_pointwise_mul_plan()["inv_group"] == G
+    got = device_mul(ctx, ref["std" if flags & BS else "mont"][:n], ref["k_words"][:n], flags=flags)
+    same(got, cut(ref["want"][flags], n), (n, flags))
+
+
+# 2
+def test_edge_scalars_on_three_bases(ctx):
+    ks = pm2.edge_scalars()
+    assert ks[:9] == [0, 1, 2, 3, R - 1, R, R + 1, 2 * R, 5 * R] and ks[11] == pm2.LAMBDA
+    # the constant of lambda * Q = (beta^2 x, y): against the independent law and the G2 MSM's own statement of it, not against the kernel
+    assert pm2.BETA2 == (-pm2.BETA - 1) % P and pm2.phi2(pm2.GEN) == g2.mul(pm2.GEN, pm2.LAMBDA)
+    src = open(os.path.join(ROOT, "gpu-acceleration_amd", "csrc", "msm_kernels_g2.hpp")).read()
+    assert "phi2(x, y) = (beta^2 x, y) = lambda * (x, y) on G2" in src
+    for b in (1, 0xC0FFEE, R - 2):
+        bs = [b] * len(ks)
+        std = pm2.bases(bs, pm2.FORM_STD)
+        got = device_mul(ctx, std, pm2.to_words(ks), flags=OS | BS)
+        same(got, pm2.expected(ks, bs, out_std=True), b)
+        xy, inf = got
+        x0, x1, y0, y1 = pm2.point_ints(std[0])
+        assert list(inf[:9]) == [1, 0, 0, 0, 0, 1, 0, 1, 1] and not xy[[0, 5, 7, 8]].any()  # 0, r, 2r, 5r: flagged and all zero
+        assert (xy[1] == std[0]).all() and (xy[6] == std[0]).all()                           # 1 * Q and (r + 1) * Q return Q's words
+        assert pm2.point_ints(xy[4]) == (x0, x1, (P - y0) % P, (P - y1) % P)                  # (r - 1) * Q = -Q: same x, y = -y
+        assert pm2.point_ints(xy[11]) == (pm2.BETA2 * x0 % P, pm2.BETA2 * x1 % P, y0, y1)     # lambda * Q = (beta^2 x, y)
+        mont = pm2.bases(bs[:12], pm2.FORM_MONT)
+        got = device_mul(ctx, mont, pm2.to_words(ks[:12]))
+        assert (got[0][1] == mont[0]).all() and not got[0][0].any() and got[1][0] == 1  # the same in Montgomery words
+
+
+# 3
+def test_identities_at_every_place_of_a_group(ctx, ref):
+    n = 2 * G + 1
+    zeros = [0, R, 2 * R, 5 * R]
+    places = {"first of a group": [0, G, 2 * G], "last of a group": [G - 1, 2 * G - 1], "a whole group": list(range(G, 2 * G)),
+              "every second lane": list(range(0, n, 2)), "all": list(range(n))}
+    want = cut(ref["want"][0], n)
+    for name, at in places.items():
+        hit = np.zeros(n, bool)
+        hit[at] = True
+        mixed = list(ref["ks"][:n])
+        for t, i in enumerate(at):
+            mixed[i] = zeros[t % 4]
+        flagged = ref["mont"][:n].copy()
+        flagged[hit] = 0xDEADBEEF  # the words of a flagged base are not read as a point
+        for how, got in (("scalars = 0 mod r", device_mul(ctx, ref["mont"][:n], pm2.to_words(mixed))),
+                         ("flagged bases", device_mul(ctx, flagged, ref["k_words"][:n], inf=hit.astype(np.uint8)))):
+            xy, inf = got
+            assert (inf[hit] == 1).all() and not xy[hit].any(), (name, how)                    # flagged, coordinates all zero
+            assert (inf[~hit] == 0).all() and (xy[~hit] == want[0][~hit]).all(), (name, how)  # every neighbour still exact
+
+
+# 4
+def test_one_scalar_for_all_points(ctx, ref):
+    import torch
+    n = 2 * G + 1
+    inf = np.zeros(n, np.uint8)
+    inf[[0, G - 1, G]] = 1
+    for k in (0, 1, R - 1, pm2.LAMBDA, pm2.patterns(0x5CA1E, 1)[0] | 1 << 255):
+        assert k < R or k >> 255
+        want = pm2.expected([k] * n, ref["bs"][:n], inf)
+        got = device_scale(ctx, ref["mont"][:n], k, inf)
+        same(got, want, ("scale against the model", hex(k)))
+        same(got, device_mul(ctx, ref["mont"][:n], pm2.to_words([k] * n), inf), ("scale against the per-element call", hex(k)))
+    same(device_scale(ctx, ref["std"][:n], 5, flags=OS | BS), pm2.expected([5] * n, ref["bs"][:n], out_std=True), "standard form in and out")
+    d_b = dev(ref["mont"][:4])
+    d_xy, d_inf = outputs(4)
+    torch.cuda.synchronize()
+    with pytest.raises(mh.MsmError) as e:
+        ctx.g2_scale_device(d_b.data_ptr(), 5, 4, d_xy.data_ptr(), d_inf.data_ptr(), flags=IM)
+    assert e.value.code == mh.ERR_BAD_ARG
+    got = host(d_xy, d_inf)
+    assert (got[0] == FILL * 0x01010101).all() and (got[1] == FILL).all()
+
+
+# 5
+def test_in_place(ctx, ref):
+    import torch
+    n = 2 * G + 1
+    inf = np.zeros(n, np.uint8)
+    inf[[3, G, n - 1]] = 1
+    want = pm2.expected(ref["ks"][:n], ref["bs"][:n], inf)
+    same(device_mul(ctx, ref["mont"][:n], ref["k_words"][:n], inf), want, "out of place")
+    d_b, d_k, d_m = dev(ref["mont"][:n]), dev(ref["k_words"][:n]), dev(inf)
+    torch.cuda.synchronize()
+    ctx.g2_pointwise_mul_device(d_b.data_ptr(), d_k.data_ptr(), n, d_b.data_ptr(), d_m.data_ptr(), d_m.data_ptr())
+    same(host(d_b, d_m), want, "in place")
+    d_b, d_m = dev(ref["mont"][:n]), dev(inf)
+    torch.cuda.synchronize()
+    ctx.g2_scale_device(d_b.data_ptr(), 7, n, d_b.data_ptr(), d_m.data_ptr(), d_m.data_ptr())
+    same(host(d_b, d_m), pm2.expected([7] * n, ref["bs"][:n], inf), "one scalar, in place")
+
+
+# 6
+def test_g2_points_of_a_proving_key():
+    """bases that are no known multiple of the generator: the entries of tests/golden/zkey_g2_points.json, infinities included, expected
+    values per point from g2.mul"""
+    with open(os.path.join(ROOT, "tests", "golden", "zkey_g2_points.json")) as f:
+        pts = json.load(f)["points"]
+    words = np.stack([np.frombuffer(bytes.fromhex(p_["mont_le_hex"]), "<u4") for p_ in pts]).astype(np.uint32)
+    inf = np.array([p_["infinity"] for p_ in pts], np.uint8)
+    n = len(pts)
+    aff = [None if inf[i] else tuple(tuple(g2.from_mont_words(words[i])[2 * c:2 * c + 2]) for c in (0, 1)) for i in range(n)]
+    live = [i for i in range(n) if not inf[i]]
+    assert len(live) >= 3 and inf.any() and all(g2.on_curve(a) for a in aff)
+    ks = pm2.patterns(0x2CE8, n)
+    ks[live[0]], ks[live[-1]] = 0, R  # two scalars = 0 mod r on live points
+    want = pm2.expected_points(ks, aff, out_std=True)
+    assert want[1][live[0]] == 1 and want[1][live[-1]] == 1 and want[1].sum() == inf.sum() + 2
+    with mh.MsmContext() as c:
+        same(device_mul(c, words, pm2.to_words(ks), inf, flags=OS), want, "zkey points")
+        same(c.g2_pointwise_mul(words, pm2.to_words(ks), mh.FORM_MONT, inf, flags=OS), want, "zkey points, host form")
+
+
+# 7
+def test_input_that_is_not_in_g2_between_live_neighbours(ctx, ref):
+    """a twist point outside G2, arbitrary words and a record with x = 0: the call returns, every neighbour is exact, and each such place holds a
+    byte of 0 or 1 -- nothing else is claimed about those places"""
+    n = 2 * G + 1
+    off = fb2.off_subgroup_point()
+    assert g2.on_curve(off) and g2.mul_raw(off, R) is not None
+    junk = np.tile(np.asarray(pm2.words(pm2.patterns(0xBAD, 1)[0]), np.uint32), 4) | np.uint32(0x80000000)  # every component above p
+    x_zero = ref["mont"][7].copy()
+    x_zero[:16] = 0
+    records = [np.array(g2.point_words(off, True), np.uint32), junk, x_zero]
+    bad_at = [1, G - 1, G, G + 5, 2 * G - 1, 2 * G]
+    bases = ref["mont"][:n].copy()
+    for t, i in enumerate(bad_at):
+        bases[i] = records[t % 3]
+    hit = np.zeros(n, bool)
+    hit[bad_at] = True
+    want = cut(ref["want"][0], n)
+    for got in (device_mul(ctx, bases, ref["k_words"][:n]), device_scale(ctx, bases, ref["ks"][0])):
+        assert set(np.unique(got[1][hit])) <= {0, 1}
+    xy, inf = device_mul(ctx, bases, ref["k_words"][:n])
+    assert (inf[~hit] == 0).all() and (xy[~hit] == want[0][~hit]).all()
+
+
+# 8
+def test_errors_write_nothing(ctx, ref):
+    import torch
+    n = 70
+    lib = mh.load_library()
+    d_b, d_k, d_m = dev(ref["mont"][:n + 1]), dev(ref["k_words"][:n + 1]), dev(np.zeros(n + 16, np.uint8))
+    d_xy, d_inf = outputs(n + 16)
+    torch.cuda.synchronize()
+    b, k, m, xy, inf = (t.data_ptr() for t in (d_b, d_k, d_m, d_xy, d_inf))
+    bad = [((None, k, n, xy, inf), {}), ((b, None, n, xy, inf), {}), ((b, k, n, None, inf), {}), ((b, k, n, xy, None), {}),
+           ((b + 4, k, n, xy, inf), {}), ((b, k + 8, n, xy, inf), {}), ((b, k, n, xy + 4, inf), {}), ((b, k, n, xy, inf + 1), {}),
+           ((b, k, n, xy, inf), {"d_inf": m + 1}), ((b, k, n, xy, inf), {"flags": 1}), ((b, k, n, xy, inf), {"flags": 4}), ((b, k, n, xy, inf), {"flags": 32})]
+    for args, kw in bad:
+        with pytest.raises(mh.MsmError) as e:
+            ctx.g2_pointwise_mul_device(*args, **kw)
+        assert e.value.code == mh.ERR_BAD_ARG, (args, kw)
+        if args[1] is not None and args[1] == k:  # the same pointers and flags through the one-scalar call
+            with pytest.raises(mh.MsmError) as e:
+                ctx.g2_scale_device(args[0], 3, *args[2:], **kw)
+            assert e.value.code == mh.ERR_BAD_ARG, (args, kw)
+    assert lib.msm_bn254_g2_scale_device(ctx._h, b, None, None, n, 0, xy, inf, None) == mh.ERR_BAD_ARG  # no scalar
+    for call in (lambda: ctx.g2_pointwise_mul_device(b, k, 0, xy, inf), lambda: ctx.g2_scale_device(b, 3, 0, xy, inf),
+                 lambda: ctx.g2_pointwise_mul(np.zeros((0, 32), np.uint32), np.zeros((0, 8), np.uint32))):
+        with pytest.raises(mh.MsmError) as e:
+            call()
+        assert e.value.code == mh.ERR_EMPTY
+    h_xy, h_inf = np.full((n, 32), FILL * 0x01010101, np.uint32), np.full(n, FILL, np.uint8)
+    hb, hk = np.ascontiguousarray(ref["mont"][:n]), np.ascontiguousarray(ref["k_words"][:n])
+    p32, p8 = lambda a: a.ctypes.data_as(mh._u32p), lambda a: a.ctypes.data_as(mh._u8p)
+    for form, flags in ((2, 0), (mh.FORM_MONT, 1), (mh.FORM_MONT, BS), (mh.FORM_MONT, 64)):
+        assert lib.msm_bn254_g2_pointwise_mul(ctx._h, p32(hb), form, None, p32(hk), n, flags, p32(h_xy), p8(h_inf)) == mh.ERR_BAD_ARG, (form, flags)
+    for args in ((None, p32(hk), p32(h_xy), p8(h_inf)), (p32(hb), None, p32(h_xy), p8(h_inf)), (p32(hb), p32(hk), None, p8(h_inf)),
+                 (p32(hb), p32(hk), p32(h_xy), None)):
+        assert lib.msm_bn254_g2_pointwise_mul(ctx._h, args[0], mh.FORM_MONT, None, args[1], n, 0, args[2], args[3]) == mh.ERR_BAD_ARG
+    got = host(d_xy, d_inf)
+    assert (got[0] == FILL * 0x01010101).all() and (got[1] == FILL).all()          # no failed call wrote anything
+    assert (h_xy == FILL * 0x01010101).all() and (h_inf == FILL).all()
+    same(device_mul(ctx, ref["mont"][:n], ref["k_words"][:n]), cut(ref["want"][0], n), "a correct call after the errors")
+
+
+# 9
+def test_two_streams(ctx, ref):
+    import torch
+    n, m = 2 * G + 1, 1000
+    d_b1, d_k1, d_b2 = dev(ref["mont"][:n]), dev(ref["k_words"][:n]), dev(ref["std"][n:n + m])
+    xy1, inf1 = outputs(n)
+    xy2, inf2 = outputs(m)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    ctx.g2_pointwise_mul_device(d_b1.data_ptr(), d_k1.data_ptr(), n, xy1.data_ptr(), inf1.data_ptr(), stream=s1.cuda_stream)
+    ctx.g2_scale_device(d_b2.data_ptr(), R - 3, m, xy2.data_ptr(), inf2.data_ptr(), flags=OS | BS, stream=s2.cuda_stream)
+    same(host(xy1, inf1), cut(ref["want"][0], n), "stream 1")
+    same(host(xy2, inf2), pm2.expected([R - 3] * m, ref["bs"][n:n + m], out_std=True), "stream 2")
+
+
+# 10
+def test_host_pointer_form_equals_device_form(ctx, ref):
+    n = 2 * G + 1
+    inf = np.zeros(n, np.uint8)
+    inf[[0, G]] = 1
+    for form, key in ((mh.FORM_MONT, "mont"), (mh.FORM_STD, "std")):
+        for flags in (0, OS):
+            xy, out_inf = ctx.g2_pointwise_mul(ref[key][:n], ref["k_words"][:n], form, inf, flags)
+            same((xy, out_inf), device_mul(ctx, ref[key][:n], ref["k_words"][:n], inf, flags | (BS if form == mh.FORM_STD else 0)), (form, flags))
+            same((xy, out_inf), pm2.expected(ref["ks"][:n], ref["bs"][:n], inf, bool(flags & OS)), (form, flags))
+    same(ctx.g2_pointwise_mul(ref["mont"][:n], ref["k_words"][:n], mh.FORM_MONT), cut(ref["want"][0], n), "no mask")
+
+
+# 11
+def test_tau_g2_update_in_hbm(ctx):
+    """tauG2[i] = tau^i * H made in HBM, then updated in place by tau'^i -- one non-default stream, nothing crossing PCIe in between -- is word
+    for word the array made from the powers of tau * tau'; it passes the subgroup check and then serves msm_bn254_g2_device as its bases"""
+    import torch
+    n = 1025
+    tau, tau2 = pm2.patterns(0x7A2, 2)
+    tau, tau2 = tau % R, tau2 % R
+    gen = fb2.base_words(pm2.GEN)
+    s = orc.gen_scalars(0xB2540017, n)
+    d_s = dev(s)
+    d_k, d_k2, d_kk = (dev(np.zeros((n, 8), np.uint32)) for _ in range(3))
+    d_xy, d_inf = outputs(n)
+    w_xy, w_inf = outputs(n)
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    q = st.cuda_stream
+    ctx.fr_powers_device(tau, d_k.data_ptr(), n, stream=q)
+    ctx.fixed_base_g2_mul_device(gen, d_k.data_ptr(), n, d_xy.data_ptr(), d_inf.data_ptr(), stream=q)
+    ctx.fr_powers_device(tau2, d_k2.data_ptr(), n, stream=q)
+    ctx.g2_pointwise_mul_device(d_xy.data_ptr(), d_k2.data_ptr(), n, d_xy.data_ptr(), d_inf.data_ptr(), d_inf.data_ptr(), stream=q)
+    assert ctx.validate_g2_device(d_xy.data_ptr(), n, d_inf_ptr=d_inf.data_ptr(), checks=mh.G2_CHECK_SUBGROUP, stream=q) is None
+    r = ctx.msm_g2_device(d_xy.data_ptr(), d_s.data_ptr(), n, d_inf.data_ptr(), stream=q)
+    ctx.fr_powers_device(tau * tau2 % R, d_kk.data_ptr(), n, stream=q)
+    ctx.fixed_base_g2_mul_device(gen, d_kk.data_ptr(), n, w_xy.data_ptr(), w_inf.data_ptr(), stream=q)
+    got = host(d_xy, d_inf)
+    same(got, host(w_xy, w_inf), "against the fixed-base call on (tau tau')^i")
+    logs = [pow(tau * tau2 % R, i, R) for i in range(n)]
+    same(cut(got, 40), fb2.expected(logs[:40]), "a prefix against the model")
+    total = sum(b * orc.words_to_int(w) for b, w in zip(logs, s)) % R
+    assert total and not r.is_infinity and r.affine_ints() == g2.mul(pm2.GEN, total)  # g2.msm of the points b_i * H, in closed form
+
+
+# 12
+def test_delta_g2_round_trip(ctx, ref):
+    """every point times 1 / delta', and back with delta'"""
+    import torch
+    n = 2 * G + 1
+    delta = pm2.patterns(0xDE17B, 1)[0] % R
+    inv = pow(delta, -1, R)
+    d_b = dev(ref["mont"][:n])
+    d_xy, d_inf = outputs(n)
+    b_xy, b_inf = outputs(n)
+    torch.cuda.synchronize()
+    ctx.g2_scale_device(d_b.data_ptr(), inv, n, d_xy.data_ptr(), d_inf.data_ptr())
+    ctx.g2_scale_device(d_xy.data_ptr(), delta, n, b_xy.data_ptr(), b_inf.data_ptr(), d_inf.data_ptr())
+    same(host(d_xy, d_inf), pm2.expected([inv] * n, ref["bs"][:n]), "times 1 / delta'")
+    same(host(b_xy, b_inf), (ref["mont"][:n], np.zeros(n, np.uint8)), "and back")
