@@ -41,9 +41,7 @@ namespace pmk {
 // next to the G2 MSM's kernels; tests/test_g2_pointwise_mul_cpu.py holds both against beta of tests/golden/glv_constants.json
 constexpr uint32_t PM2_BETA2_STD[8] = {0x77fffffeu, 0x57634731u, 0xacdb5c4fu, 0xd4f263f1u, 0xa0d48bacu, 0x59e26bceu, 0x00000000u, 0x00000000u};
 
-struct Pm2Plan {  // == msm_pointwise_g2_plan_t
-    uint32_t inv_group, ladder_bits, table_points, reserved;
-};
+using Pm2Plan = PmPlan;  // == msm_pointwise_g2_plan_t: the same four words
 inline Pm2Plan pm2_plan() { return Pm2Plan{FB_GROUP, PM_LADDER_BITS, PM_TABLE_POINTS, 0}; }
 
 struct Pm2Lane {  // what a lane keeps in registers: x, beta^2 x, y (canonical: P1 = (x, +-y), P2 = (bx, +-y) by s.neg1, s.neg2), S = (sx, sy) canonical

@@ -1,6 +1,6 @@
 // msm_fr_vectors.inc -- the scalars of a setup made in HBM, behind the C ABI: msm_bn254_fr_vector_plan (host only), msm_bn254_fr_powers_device,
 // msm_bn254_fr_batch_inverse_device, msm_bn254_fr_batch_inverse, msm_bn254_fr_lagrange_device, msm_bn254_fr_lincomb_device.  Included by
-// msm_hip.hip after msm_fixed_base_g2.inc; the per-lane routines and the kernels are fr_vectors_bn254.hpp.
+// msm_hip.hip after msm_fixed_base.inc; the per-lane routines and the kernels are fr_vectors_bn254.hpp.
 //
 // Nothing is kept on the context: every constant a kernel needs (the scale, the powers base^(2^k), the change of form) is prepared on the host
 // and travels BY VALUE with the launch, no table, no scratch array, no event.  So two calls on two streams do not wait for each other, and a

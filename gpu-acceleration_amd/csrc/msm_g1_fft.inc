@@ -96,7 +96,7 @@ int32_t g1_fft_enqueue(msm_ctx* c, uint32_t* d_xy, uint8_t* d_inf, uint32_t k, s
     if (k == 0) {  // the form and the flag only: one pass with the scalar 1
         const uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
         const PmSplit uni = pm_split_host(one);
-        return pointwise_enqueue(c, d_xy, d_inf, nullptr, &uni, points, flags & (MSM_PM_BASES_STD | MSM_FB_OUT_STD), d_xy, d_inf, st);
+        return pointwise_enqueue<HostG1>(c, d_xy, d_inf, nullptr, &uni, points, flags & (MSM_PM_BASES_STD | MSM_FB_OUT_STD), d_xy, d_inf, st);
     }
     const uint32_t* tw = nullptr;
     int32_t rc;
@@ -121,7 +121,7 @@ int32_t g1_fft_enqueue(msm_ctx* c, uint32_t* d_xy, uint8_t* d_inf, uint32_t k, s
     uint32_t n_std[8] = {1u << k, 0, 0, 0, 0, 0, 0, 0}, ninv_std[8];
     nttk::fr_to_std(ninv_std, nttk::fr_inv(nttk::fr_from_std(n_std)));
     const PmSplit uni = pm_split_host(ninv_std);
-    return pointwise_enqueue(c, d_xy, d_inf, nullptr, &uni, points, flags & MSM_FB_OUT_STD, d_xy, d_inf, st);
+    return pointwise_enqueue<HostG1>(c, d_xy, d_inf, nullptr, &uni, points, flags & MSM_FB_OUT_STD, d_xy, d_inf, st);
 }
 
 }  // namespace

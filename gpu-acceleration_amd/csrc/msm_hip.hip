@@ -180,9 +180,8 @@ constexpr int STREAM_SLOTS = 3;
 struct NttState;  // msm_ntt.inc
 struct R1csState;  // msm_r1cs.inc
 struct FixedBaseState;  // msm_fixed_base.inc
-struct FixedBaseG2State;  // msm_fixed_base_g2.inc
+struct FixedBaseG2State;  // msm_fixed_base.inc
 struct PointwiseState;  // msm_pointwise.inc
-struct G2PointwiseState;  // msm_g2_pointwise.inc
 struct G1FftState;  // msm_g1_fft.inc
 struct msm_ctx {
     std::mutex mu;
@@ -245,9 +244,8 @@ struct msm_ctx {
     NttState* ntt = nullptr;      // tables and scratch of the scalar-field transforms, made by the first of them (msm_ntt.inc)
     R1csState* r1cs = nullptr;    // the resident constraint matrices and their scratch, made by the first upload (msm_r1cs.inc)
     FixedBaseState* fixed_base = nullptr;  // the window table of the latest fixed base, made by the first such call (msm_fixed_base.inc)
-    FixedBaseG2State* fixed_base_g2 = nullptr;  // the same for G2, with the scratch array of its two-kernel chunks (msm_fixed_base_g2.inc)
-    PointwiseState* pointwise = nullptr;  // the staging arrays of the host-pointer element-wise multiplication, made by its first call (msm_pointwise.inc)
-    G2PointwiseState* g2_pointwise = nullptr;  // the same for the G2 call (msm_g2_pointwise.inc)
+    FixedBaseG2State* fixed_base_g2 = nullptr;  // the same for G2, with the scratch array of its two-kernel chunks (msm_fixed_base.inc)
+    PointwiseState* pointwise[2] = {};  // per group (PointSide<G>::RESULT) the staging arrays of the host-pointer element-wise multiplication, made by its first call (msm_pointwise.inc)
     G1FftState* g1_fft = nullptr;  // the twiddle tables of the G1 group transform, one per size, and the staging arrays of its host-pointer form (msm_g1_fft.inc)
 };
 
@@ -255,10 +253,8 @@ namespace {
 
 void ntt_release(msm_ctx* c);  // msm_ntt.inc
 void r1cs_release(msm_ctx* c);  // msm_r1cs.inc
-void fixed_base_release(msm_ctx* c);  // msm_fixed_base.inc
-void fixed_base_g2_release(msm_ctx* c);  // msm_fixed_base_g2.inc
-void pointwise_release(msm_ctx* c);  // msm_pointwise.inc
-void g2_pointwise_release(msm_ctx* c);  // msm_g2_pointwise.inc
+void fixed_base_release(msm_ctx* c);  // msm_fixed_base.inc (both groups)
+void pointwise_release(msm_ctx* c);  // msm_pointwise.inc (both groups)
 void g1_fft_release(msm_ctx* c);  // msm_g1_fft.inc
 
 int32_t fail(msm_ctx* c, int32_t code, const char* fmt, ...) {
@@ -1587,9 +1583,7 @@ void msm_ctx_destroy(msm_ctx* c) {
         ntt_release(c);
         r1cs_release(c);
         fixed_base_release(c);
-        fixed_base_g2_release(c);
         pointwise_release(c);
-        g2_pointwise_release(c);
         g1_fft_release(c);
         DevBuf* bufs[] = {&c->bases,   &c->inf,       &c->scalars, &c->digits,  &c->ranks,  &c->sorted, &c->hist,
                           &c->offsets, &c->blocksums, &c->buckets, &c->rc,      &c->flags,  &c->pow2,
@@ -2113,10 +2107,8 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 #include "msm_ntt.inc"
 #include "msm_r1cs.inc"
 #include "msm_fixed_base.inc"
-#include "msm_fixed_base_g2.inc"
 #include "msm_fr_vectors.inc"
 #include "msm_pointwise.inc"
-#include "msm_g2_pointwise.inc"
 #include "msm_g1_fft.inc"
 
 #ifdef MSM_HIP_TEST_HOOKS

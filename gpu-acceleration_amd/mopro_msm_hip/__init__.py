@@ -138,12 +138,7 @@ class PointwisePlan(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
-class G2PointwisePlan(C.Structure):
-    """msm_pointwise_g2_plan_t: the same three figures for the G2 element-wise multiplication"""
-    _fields_ = [("inv_group", C.c_uint32), ("ladder_bits", C.c_uint32), ("table_points", C.c_uint32), ("reserved", C.c_uint32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+G2PointwisePlan = PointwisePlan  # msm_pointwise_g2_plan_t: the same three figures for the G2 element-wise multiplication
 
 
 class G1FftPlan(C.Structure):
@@ -872,15 +867,29 @@ class MsmContext:
     def fr_vector_plan():
         return fr_vector_plan()
 
+    # -- the host-array forms of the fixed-base and the element-wise calls; words: 16 per G1 point, 32 per G2 point; fn: the library's function ---
+    def _fixed_base_host(self, words, fn, base, scalars, form, window_bits, flags):
+        b, k = _words(base, words), _words(scalars, 8)
+        xy, inf = np.zeros((k.shape[0], words), np.uint32), np.zeros(k.shape[0], np.uint8)
+        self._check(fn(self._h, _p32(b), form, _p32(k), k.shape[0], window_bits, flags, _p32(xy), inf.ctypes.data_as(_u8p)))
+        return xy, inf
+
+    def _pointwise_host(self, words, fn, bases, scalars, form, inf, flags):
+        b, k = _words(bases, words), _words(scalars, 8)
+        if b.shape[0] != k.shape[0]:
+            raise MsmError(ERR_BAD_ARG, "as many scalars as bases")
+        xy, out_inf = np.zeros((k.shape[0], words), np.uint32), np.zeros(k.shape[0], np.uint8)
+        inf, inf_p = self._inf_ptr(inf)
+        if inf is not None and inf.size != k.shape[0]:
+            raise MsmError(ERR_BAD_ARG, "as many infinity bytes as bases")
+        self._check(fn(self._h, _p32(b), form, inf_p, _p32(k), k.shape[0], flags, _p32(xy), out_inf.ctypes.data_as(_u8p)))
+        return xy, out_inf
+
     # -- BN254 G1 fixed base: out[i] = k_i * P, one base, n affine points (the queries of a setup made in HBM) ---
     def fixed_base_mul(self, base, scalars, form=FORM_STD, window_bits=0, flags=0):
         """host arrays: the base (16 words x, y in `form`) and n x 8 scalar words (any 256-bit patterns; flags NTT_IN_MONT: arkworks Fr.0 words)
         -> (n x 16 words xy, n bytes inf); the coordinates are arkworks Montgomery words, standard form with FB_OUT_STD"""
-        b, k = _words(base, 16), _words(scalars, 8)
-        xy, inf = np.zeros((k.shape[0], 16), np.uint32), np.zeros(k.shape[0], np.uint8)
-        self._check(self._lib.msm_bn254_g1_fixed_base_mul(self._h, _p32(b), form, _p32(k), k.shape[0], window_bits, flags, _p32(xy),
-                                                          inf.ctypes.data_as(_u8p)))
-        return xy, inf
+        return self._fixed_base_host(16, self._lib.msm_bn254_g1_fixed_base_mul, base, scalars, form, window_bits, flags)
 
     def fixed_base_mul_device(self, base, d_scalars, n, d_out_xy, d_out_inf, form=FORM_STD, window_bits=0, flags=0, stream=None):
         """raw device pointers: n x 8 scalar words in, n x 16 words xy and n bytes inf out; the base is a host array; enqueued on `stream`
@@ -893,11 +902,7 @@ class MsmContext:
     def fixed_base_g2_mul(self, base, scalars, form=FORM_STD, window_bits=0, flags=0):
         """host arrays: the base (32 words x.c0, x.c1, y.c0, y.c1 in `form`) and n x 8 scalar words (flags NTT_IN_MONT: arkworks Fr.0 words)
         -> (n x 32 words xy, n bytes inf); the coordinates are arkworks Montgomery words, standard form with FB_OUT_STD"""
-        b, k = _words(base, 32), _words(scalars, 8)
-        xy, inf = np.zeros((k.shape[0], 32), np.uint32), np.zeros(k.shape[0], np.uint8)
-        self._check(self._lib.msm_bn254_g2_fixed_base_mul(self._h, _p32(b), form, _p32(k), k.shape[0], window_bits, flags, _p32(xy),
-                                                          inf.ctypes.data_as(_u8p)))
-        return xy, inf
+        return self._fixed_base_host(32, self._lib.msm_bn254_g2_fixed_base_mul, base, scalars, form, window_bits, flags)
 
     def fixed_base_g2_mul_device(self, base, d_scalars, n, d_out_xy, d_out_inf, form=FORM_STD, window_bits=0, flags=0, stream=None):
         """raw device pointers: n x 8 scalar words in, n x 32 words xy and n bytes inf out (what msm_g2_device takes); the base is a host
@@ -911,16 +916,7 @@ class MsmContext:
         """host arrays: n x 16 base words (x, y in `form`), n x 8 scalar words (any 256-bit patterns; flags NTT_IN_MONT: arkworks Fr.0 words) and
         optionally n infinity bytes -> (n x 16 words xy, n bytes inf); the coordinates are arkworks Montgomery words, standard form with
         FB_OUT_STD.  The bases are not validated (validate_g1 does that)"""
-        b, k = _words(bases, 16), _words(scalars, 8)
-        if b.shape[0] != k.shape[0]:
-            raise MsmError(ERR_BAD_ARG, "as many scalars as bases")
-        xy, out_inf = np.zeros((k.shape[0], 16), np.uint32), np.zeros(k.shape[0], np.uint8)
-        inf, inf_p = self._inf_ptr(inf)
-        if inf is not None and inf.size != k.shape[0]:
-            raise MsmError(ERR_BAD_ARG, "as many infinity bytes as bases")
-        self._check(self._lib.msm_bn254_g1_pointwise_mul(self._h, _p32(b), form, inf_p, _p32(k), k.shape[0], flags, _p32(xy),
-                                                         out_inf.ctypes.data_as(_u8p)))
-        return xy, out_inf
+        return self._pointwise_host(16, self._lib.msm_bn254_g1_pointwise_mul, bases, scalars, form, inf, flags)
 
     def pointwise_mul_device(self, d_bases, d_scalars, n, d_out_xy, d_out_inf, d_inf=None, flags=0, stream=None):
         """raw device pointers: n x 16 base words, n x 8 scalar words and optionally n infinity bytes in, n x 16 words xy and n bytes inf out;
@@ -942,16 +938,7 @@ class MsmContext:
         """host arrays: n x 32 base words (in `form`), n x 8 scalar words (any 256-bit patterns; flags NTT_IN_MONT: arkworks Fr.0 words) and
         optionally n infinity bytes -> (n x 32 words xy, n bytes inf); the components are arkworks Montgomery words, standard form with
         FB_OUT_STD.  The bases must be points of G2 and are not validated (validate_g2 with G2_CHECK_SUBGROUP does that)"""
-        b, k = _words(bases, 32), _words(scalars, 8)
-        if b.shape[0] != k.shape[0]:
-            raise MsmError(ERR_BAD_ARG, "as many scalars as bases")
-        xy, out_inf = np.zeros((k.shape[0], 32), np.uint32), np.zeros(k.shape[0], np.uint8)
-        inf, inf_p = self._inf_ptr(inf)
-        if inf is not None and inf.size != k.shape[0]:
-            raise MsmError(ERR_BAD_ARG, "as many infinity bytes as bases")
-        self._check(self._lib.msm_bn254_g2_pointwise_mul(self._h, _p32(b), form, inf_p, _p32(k), k.shape[0], flags, _p32(xy),
-                                                         out_inf.ctypes.data_as(_u8p)))
-        return xy, out_inf
+        return self._pointwise_host(32, self._lib.msm_bn254_g2_pointwise_mul, bases, scalars, form, inf, flags)
 
     def g2_pointwise_mul_device(self, d_bases, d_scalars, n, d_out_xy, d_out_inf, d_inf=None, flags=0, stream=None):
         """raw device pointers: n x 32 base words, n x 8 scalar words and optionally n infinity bytes in, n x 32 words xy and n bytes inf out;

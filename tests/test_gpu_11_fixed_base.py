@@ -225,3 +225,13 @@ def test_against_the_hooks_generator():
         h.generate_device(seed, 0, n, d_b.data_ptr(), None)
         hook = host(d_b, dev(np.zeros(n, np.uint8)))[0]
         same(device_mul(h, fb.base_words(fb.GEN), orc.gen_scalars(seed, n, nonzero=True)), (hook, np.zeros(n, np.uint8)), "hook")
+
+
+# 9
+def test_the_staging_boundary_of_the_host_form(ctx, ref):
+    """2^20 + 513 scalars: the host-pointer form stages 2^20 at a time, so its loop runs twice"""
+    n = (1 << 20) + 513
+    reps = -(-n // 513)
+    words = np.tile(ref[0][:513], (reps, 1))[:n]
+    want = (np.tile(ref[1][0][0][:513], (reps, 1))[:n], np.tile(ref[1][0][1][:513], reps)[:n])
+    same(ctx.fixed_base_mul(fb.base_words(fb.GEN), words), want, "host form")

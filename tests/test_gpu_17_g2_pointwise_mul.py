@@ -352,3 +352,19 @@ def test_delta_g2_round_trip(ctx, ref):
     ctx.g2_scale_device(d_xy.data_ptr(), delta, n, b_xy.data_ptr(), b_inf.data_ptr(), d_inf.data_ptr())
     same(host(d_xy, d_inf), pm2.expected([inv] * n, ref["bs"][:n]), "times 1 / delta'")
     same(host(b_xy, b_inf), (ref["mont"][:n], np.zeros(n, np.uint8)), "and back")
+
+
+# 13
+def test_the_staging_boundary_on_both_forms(ctx, ref):
+    """2^19 + 513 points: the host-pointer form stages 2^19 at a time, so its loop runs twice, with one flagged base in each step"""
+    n = (1 << 19) + 513
+    reps = -(-n // 513)
+    bases = np.tile(ref["mont"][:513], (reps, 1))[:n]
+    words = np.tile(ref["k_words"][:513], (reps, 1))[:n]
+    want = (np.tile(ref["want"][0][0][:513], (reps, 1))[:n], np.tile(ref["want"][0][1][:513], reps)[:n])
+    inf = np.zeros(n, np.uint8)
+    for at in (5, (1 << 19) + 7):  # neither is an identity of the expectation already
+        assert want[1][at] == 0
+        inf[at], want[0][at], want[1][at] = 1, 0, 1
+    same(ctx.g2_pointwise_mul(bases, words, mh.FORM_MONT, inf), want, "host form")
+    same(device_mul(ctx, bases, words, inf), want, "device form")
