@@ -53,6 +53,7 @@
 #include "msm_kernels_pointwise.hpp"
 #include "msm_kernels_g2_pointwise.hpp"
 #include "msm_kernels_g1_fft.hpp"
+#include "msm_kernels_g2_fft.hpp"
 
 namespace {
 
@@ -182,7 +183,7 @@ struct R1csState;  // msm_r1cs.inc
 struct FixedBaseState;  // msm_fixed_base.inc
 struct FixedBaseG2State;  // msm_fixed_base.inc
 struct PointwiseState;  // msm_pointwise.inc
-struct G1FftState;  // msm_g1_fft.inc
+struct GroupFftState;  // msm_g1_fft.inc
 struct msm_ctx {
     std::mutex mu;
     Knobs knobs;
@@ -246,7 +247,7 @@ struct msm_ctx {
     FixedBaseState* fixed_base = nullptr;  // the window table of the latest fixed base, made by the first such call (msm_fixed_base.inc)
     FixedBaseG2State* fixed_base_g2 = nullptr;  // the same for G2, with the scratch array of its two-kernel chunks (msm_fixed_base.inc)
     PointwiseState* pointwise[2] = {};  // per group (PointSide<G>::RESULT) the staging arrays of the host-pointer element-wise multiplication, made by its first call (msm_pointwise.inc)
-    G1FftState* g1_fft = nullptr;  // the twiddle tables of the G1 group transform, one per size, and the staging arrays of its host-pointer form (msm_g1_fft.inc)
+    GroupFftState* group_fft = nullptr;  // the twiddle tables of the G1 and G2 group transforms, one per size for both, and the staging arrays of their host-pointer forms (msm_g1_fft.inc)
 };
 
 namespace {
@@ -255,7 +256,7 @@ void ntt_release(msm_ctx* c);  // msm_ntt.inc
 void r1cs_release(msm_ctx* c);  // msm_r1cs.inc
 void fixed_base_release(msm_ctx* c);  // msm_fixed_base.inc (both groups)
 void pointwise_release(msm_ctx* c);  // msm_pointwise.inc (both groups)
-void g1_fft_release(msm_ctx* c);  // msm_g1_fft.inc
+void group_fft_release(msm_ctx* c);  // msm_g1_fft.inc (both groups)
 
 int32_t fail(msm_ctx* c, int32_t code, const char* fmt, ...) {
     char buf[512];
@@ -1584,7 +1585,7 @@ void msm_ctx_destroy(msm_ctx* c) {
         r1cs_release(c);
         fixed_base_release(c);
         pointwise_release(c);
-        g1_fft_release(c);
+        group_fft_release(c);
         DevBuf* bufs[] = {&c->bases,   &c->inf,       &c->scalars, &c->digits,  &c->ranks,  &c->sorted, &c->hist,
                           &c->offsets, &c->blocksums, &c->buckets, &c->rc,      &c->flags,  &c->pow2,
                           &c->sorttmp, &c->tilecounts, &c->ibases, &c->longlist, &c->longdone, &c->midlist, &c->ccounts, &c->cregion, &c->bigslot, &c->big,

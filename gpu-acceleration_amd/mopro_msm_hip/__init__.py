@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "msm_bn254_g1_pointwise_mul_plan", "msm_bn254_g1_pointwise_mul_device", "msm_bn254_g1_scale_device", "msm_bn254_g1_pointwise_mul",
     "msm_bn254_g1_fft_plan", "msm_bn254_g1_fft_device", "msm_bn254_g1_fft",
     "msm_bn254_g2_pointwise_mul_plan", "msm_bn254_g2_pointwise_mul_device", "msm_bn254_g2_scale_device", "msm_bn254_g2_pointwise_mul",
+    "msm_bn254_g2_fft_plan", "msm_bn254_g2_fft_device", "msm_bn254_g2_fft",
 ]
 ABI_VERSION = 7  # == MSM_HIP_ABI_VERSION of include/msm_hip.h this binding was written against (checked when a library is loaded)
 ERR_RCCL = -8
@@ -147,6 +148,9 @@ class G1FftPlan(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+G2FftPlan = G1FftPlan  # msm_g2_fft_plan_t: the same four fields for the G2 group transform (one twiddle table serves both groups)
 
 
 # msm_r1cs_coef_t: matrix, row, col, 8 value words -- 44 bytes, the layout of one entry of a zkey's coefficient section
@@ -253,6 +257,9 @@ def bind_product_abi(L):
     L.msm_bn254_g1_fft_plan.argtypes = [C.c_uint32, C.POINTER(G1FftPlan)]
     L.msm_bn254_g1_fft_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_size_t, C.c_uint32, vp]
     L.msm_bn254_g1_fft.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_uint32, C.c_size_t, C.c_uint32, _u32p, _u8p]
+    L.msm_bn254_g2_fft_plan.argtypes = [C.c_uint32, C.POINTER(G2FftPlan)]
+    L.msm_bn254_g2_fft_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_size_t, C.c_uint32, vp]
+    L.msm_bn254_g2_fft.argtypes = [vp, _u32p, C.c_uint32, _u8p, C.c_uint32, C.c_size_t, C.c_uint32, _u32p, _u8p]
     L.msm_bn254_fr_vector_plan.argtypes = [C.POINTER(FrVectorPlan)]
     L.msm_bn254_fr_powers_device.argtypes = [vp, _u32p, _u32p, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp]
     L.msm_bn254_fr_batch_inverse_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
@@ -470,6 +477,16 @@ def g1_fft_plan(log_n):
     rc = lib.msm_bn254_g1_fft_plan(log_n, C.byref(p))
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g1_fft_plan failed ({rc})")
+    return p.as_dict()
+
+
+def g2_fft_plan(log_n):
+    """the same for the G2 group transform, as a dict of msm_g2_fft_plan_t: the table is the G1 transform's (host only: no context, no GPU)"""
+    p = G2FftPlan()
+    lib = load_library()
+    rc = lib.msm_bn254_g2_fft_plan(log_n, C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_g2_fft_plan failed ({rc})")
     return p.as_dict()
 
 
@@ -985,6 +1002,38 @@ class MsmContext:
     @staticmethod
     def g1_fft_plan(log_n):
         return g1_fft_plan(log_n)
+
+    # -- BN254 G2 group transform: the same over G2 records; the inverse makes L_i(tau) * H from the tauG2 section tau^j * H -------------------
+    def g2_fft(self, xy, log_n, form=FORM_STD, inf=None, batch=1, flags=0, out_xy=None, out_inf=None):
+        """host arrays: batch * 2^log_n x 32 words (x.c0 x.c1 y.c0 y.c1 in `form`) and optionally as many infinity bytes -> (xy, inf) of the
+        transform, natural order in and out; flags NTT_INVERSE (1/n included) / FB_OUT_STD (default: arkworks Montgomery words).  out_xy /
+        out_inf: contiguous arrays to write into; out_xy may be xy and out_inf may be inf (in place).  The points must be points of G2 and
+        are not validated"""
+        a = _words(xy, 32)
+        n = batch << log_n
+        if a.shape[0] != n:
+            raise MsmError(ERR_BAD_ARG, "batch * 2^log_n points")
+        inf, inf_p = self._inf_ptr(inf)
+        if inf is not None and inf.size != n:
+            raise MsmError(ERR_BAD_ARG, "as many infinity bytes as points")
+        if out_xy is None:
+            out_xy = np.zeros((n, 32), np.uint32)
+        if out_inf is None:
+            out_inf = np.zeros(n, np.uint8)
+        for o, dt, size in ((out_xy, np.uint32, n * 32), (out_inf, np.uint8, n)):
+            if not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.flags.writeable and o.size == size):
+                raise MsmError(ERR_BAD_ARG, "the output arrays are contiguous, writeable, uint32 resp. uint8, of the input's size")
+        self._check(self._lib.msm_bn254_g2_fft(self._h, _p32(a), form, inf_p, log_n, batch, flags, _p32(out_xy), out_inf.ctypes.data_as(_u8p)))
+        return out_xy, out_inf
+
+    def g2_fft_device(self, d_xy, d_inf, log_n, batch=1, flags=0, stream=None):
+        """raw device pointers, in place: batch arrays of 2^log_n x 32 words and batch * 2^log_n infinity bytes (required); flags NTT_INVERSE /
+        PM_BASES_STD / FB_OUT_STD; enqueued on `stream` (None: the context's).  The twiddle tables are those g1_fft_device keeps"""
+        self._check(self._lib.msm_bn254_g2_fft_device(self._h, d_xy, d_inf, log_n, batch, flags, stream))
+
+    @staticmethod
+    def g2_fft_plan(log_n):
+        return g2_fft_plan(log_n)
 
     def set_stage_timing(self, enabled=True):
         self._check(self._lib.msm_set_stage_timing(self._h, int(bool(enabled))))

@@ -602,7 +602,8 @@ int32_t msm_bn254_g1_pointwise_mul(msm_ctx *ctx, const uint32_t *bases_xy, uint3
  *      n / 2 powers of w in standard form (msm_g1_fft_plan_t.table_bytes; one table serves both directions), built on the call's stream by its
  *      first use.  A call on ANOTHER stream waits for the event behind that build, so calls of a context on two streams that first build a
  *      table order themselves; afterwards they do not wait for each other, and the caller orders calls that share an array.
- *      A coset form is not offered: multiply by g^i with msm_bn254_g1_pointwise_mul_device.  There is no G2 sibling.
+ *      A coset form is not offered: multiply by g^i with msm_bn254_g1_pointwise_mul_device.  The G2 sibling is
+ *      msm_bn254_g2_fft_device below; it shares this call's twiddle tables.
  *      Errors: a NULL or misaligned pointer, an unknown flag bit, log_n > 28, batch * n > 2^36, a bad base_form: MSM_ERR_BAD_ARG; batch == 0:
  *      MSM_ERR_EMPTY; allocation failure: MSM_ERR_OOM.  A failed call writes nothing and the context stays usable. ---- */
 typedef struct {
@@ -665,6 +666,45 @@ int32_t msm_bn254_g2_scale_device(msm_ctx *ctx, const void *d_bases_xy, const vo
  * inf_mask NULL: no point is flagged; out_xy may be bases_xy and out_inf may be inf_mask. */
 int32_t msm_bn254_g2_pointwise_mul(msm_ctx *ctx, const uint32_t *bases_xy, uint32_t base_form, const uint8_t *inf_mask, const uint32_t *scalars,
                                    size_t n, uint32_t flags, uint32_t *out_xy, uint8_t *out_inf);
+
+/* ---- BN254 G2 group transform (ABI 7): the discrete Fourier transform over G2 POINTS, in place, natural order in and out
+ *      -- the G1 group transform above on the records of the G2 element-wise calls, with its contract word for word:
+ *          forward:  out[j] = sum_i w^(ij) * in[i];     with MSM_NTT_INVERSE:  out[i] = n^-1 * sum_j w^(-ij) * in[j]
+ *      w = msm_bn254_fr_root_of_unity(log_n), n = 2^log_n.  The inverse turns the tauG2 section tauG2[j] = tau^j * H of a powers-of-tau file into
+ *      L_i(tau) * H without anybody knowing tau (the G2 half of snarkjs "powersoftau prepare phase2").  A bit-reversal sweep, then log_n radix-2
+ *      stages of one lane per butterfly, each the ladder of the G2 element-wise multiplication, two complete additions and one normalisation
+ *      through the norms; the first stage (every twiddle 1) runs no ladder; no scratch array.
+ *      d_xy: batch contiguous arrays of n x 32 words (x.c0 x.c1 y.c0 y.c1, the records of msm_bn254_g2_pointwise_mul_device); d_inf: batch * n
+ *      bytes (nonzero = the point at infinity, its words ignored), REQUIRED.  Both device memory, 16-byte aligned, read and written.  flags:
+ *      MSM_NTT_INVERSE (1u), MSM_PM_BASES_STD (16u), MSM_FB_OUT_STD (8u); any other bit is MSM_ERR_BAD_ARG.  Outputs: canonical components,
+ *      word-exact; the identity is inf = 1 with 32 zero words, every other place has inf = 0.  log_n == 0 only converts the form and
+ *      canonicalises the flag.  log_n <= 28 and batch * n <= 2^36.
+ *      THE INPUTS MUST BE POINTS OF G2, the subgroup of order r, not only of the twist: the twist's cofactor is not 1, and reading a twiddle
+ *      modulo r and the endomorphism of the ladder are only right in G2.  The call does NOT validate them; msm_bn254_g2_validate(_device) with
+ *      MSM_G2_CHECK_SUBGROUP does.  Anything else gives meaningless points at the places that depend on it (after log_n stages: every place of
+ *      its array), never a fault and never a change to another array of the batch: every address is a function of the lane index only.
+ *      Stream-ordered on hip_stream (NULL = the context's stream): the call returns when enqueued.  The twiddle tables are the G1 transform's:
+ *      one table per log_n >= 2 on the context serves both groups and both directions (msm_g2_fft_plan_t.table_bytes ==
+ *      msm_g1_fft_plan_t.table_bytes), built on the stream of whichever call first needs it; a call on ANOTHER stream waits for the event behind
+ *      that build.  A coset form is not offered (multiply by g^i with msm_bn254_g2_pointwise_mul_device), later stages do not skip their w = 1
+ *      butterflies, and one call runs on one GPU.
+ *      Errors, as for G1: a NULL or misaligned pointer, an unknown flag bit, log_n > 28, batch * n > 2^36, a bad base_form: MSM_ERR_BAD_ARG;
+ *      batch == 0: MSM_ERR_EMPTY; allocation failure: MSM_ERR_OOM.  A failed call writes nothing and the context stays usable. ---- */
+typedef struct {
+    uint16_t stages;         /* butterfly launches per 2^30 butterflies: log_n */
+    uint16_t ladder_stages;  /* ... of them with a scalar multiplication per butterfly: log_n - 1 (0 for log_n == 0) */
+    uint32_t inv_group;      /* butterflies that share one field inversion (twice per ladder stage: the slopes' norms, the 2 * inv_group outputs) */
+    uint64_t table_bytes;    /* kept on the context for this size, shared with the G1 transform: n / 2 twiddles of 32 bytes (0 below log_n = 2) */
+} msm_g2_fft_plan_t;
+
+/* host only, no context */
+int32_t msm_bn254_g2_fft_plan(uint32_t log_n, msm_g2_fft_plan_t *out);
+int32_t msm_bn254_g2_fft_device(msm_ctx *ctx, void *d_xy, void *d_inf, uint32_t log_n, size_t batch, uint32_t flags, void *hip_stream);
+/* on host pointers, blocking.  base_form: MSM_FORM_STD / _MONT (MSM_PM_BASES_STD is not taken here); inf NULL: nothing is flagged; out_xy may be
+ * xy and out_inf may be inf.  The whole batch is staged in device memory (129 bytes per point, kept on the context and shared with
+ * msm_bn254_g1_fft): a transform cannot be chunked.  Pageable memory is pinned in place like every host-pointer call. */
+int32_t msm_bn254_g2_fft(msm_ctx *ctx, const uint32_t *xy, uint32_t base_form, const uint8_t *inf, uint32_t log_n, size_t batch, uint32_t flags,
+                         uint32_t *out_xy, uint8_t *out_inf);
 
 /* ---- BN254 scalar field Fr: the scalars of a setup made in HBM (ABI 7) -- what the fixed-base calls above read as k_i:
  *      powers of tau (the H query, KZG), element-wise inverses, the Lagrange coefficients L_i(tau) of the transforms' domain, and the linear

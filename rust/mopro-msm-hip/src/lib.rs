@@ -315,6 +315,24 @@ extern "C" {
     ) -> i32;
 }
 
+/// msm_g2_fft_plan_t: the same four fields for the G2 group transform (table_bytes is the G1 plan's: one table serves both groups)
+pub type MsmG2FftPlan = MsmG1FftPlan;
+
+// The same transform over G2 records of 32 words (include/msm_hip.h "G2 group transform"): the inverse turns the tauG2
+// section tau^j * H into L_i(tau) * H without tau.  The points must be points of G2 and are not validated.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_g2_fft_plan(log_n: u32, out: *mut MsmG2FftPlan) -> i32;
+    pub fn msm_bn254_g2_fft_device(
+        ctx: *mut MsmCtx, d_xy: *mut core::ffi::c_void, d_inf: *mut core::ffi::c_void, log_n: u32, batch: usize, flags: u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_g2_fft(
+        ctx: *mut MsmCtx, xy: *const u32, base_form: u32, inf: *const u8, log_n: u32, batch: usize, flags: u32, out_xy: *mut u32,
+        out_inf: *mut u8,
+    ) -> i32;
+}
+
 /// msm_pointwise_g2_plan_t: the same three figures for the G2 element-wise multiplication
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
