@@ -147,6 +147,51 @@ int32_t msm_test_g2_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uint32_
     HIPCHK(c, hipMemcpy(out, dout, n * a_words * 4, hipMemcpyDeviceToHost));
     return MSM_OK;
 }
+// the G1 group law on raw limb records (msmk::k_test_g1_raw and the two eight-lane kernels): checks, alloc / copy / launch / sync as msm_test_g2_op
+int32_t msm_test_g1_raw_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+    if (!c || !a || !out) return MSM_ERR_BAD_ARG;
+    if (op > MSM_OP_G1_RAW_ADD_WIDE_HBM) return fail(c, MSM_ERR_BAD_ARG, "unknown raw G1 op %u", op);
+    if (op != MSM_OP_G1_RAW_DBL && !b) return MSM_ERR_BAD_ARG;
+    if (n == 0) return MSM_ERR_EMPTY;
+    if (n > 0x7FFFFFFFull / msmk::XW) return fail(c, MSM_ERR_BAD_ARG, "n too large");
+    const bool m256 = op == MSM_OP_G1_RAW_MADD_M256 || op == MSM_OP_G1_RAW_MADD_M256_NEG;
+    const size_t a_words = msmk::XW;
+    const size_t b_words = op == MSM_OP_G1_RAW_DBL ? 0 : m256 ? 16 : op <= MSM_OP_G1_RAW_MADD_NEG_RAW ? 18 : (size_t)msmk::XW;
+    // a limb of 2^29 or more could overflow a column accumulator of the multiplication: a malformed test is refused, not run
+    // (the 16 words of the M256 operations are not limbs: fp_unpack_shl5 takes any 256 bits)
+    for (size_t i = 0; i < n * a_words; i++)
+        if (a[i] > bn254::FP_MASK) return fail(c, MSM_ERR_BAD_ARG, "a: word %zu of record %zu is not a 29-bit limb", i % a_words, i / a_words);
+    for (size_t i = 0; !m256 && i < n * b_words; i++)
+        if (b[i] > bn254::FP_MASK) return fail(c, MSM_ERR_BAD_ARG, "b: word %zu of record %zu is not a 29-bit limb", i % b_words, i / b_words);
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    DevTmp ta, tb_, tout;  // freed on every exit path
+    HIPCHK(c, hipMalloc(&ta.p, n * a_words * 4));
+    HIPCHK(c, hipMalloc(&tout.p, n * a_words * 4));
+    HIPCHK(c, hipMemcpy(ta.p, a, n * a_words * 4, hipMemcpyHostToDevice));
+    if (b_words) {
+        HIPCHK(c, hipMalloc(&tb_.p, n * b_words * 4));
+        HIPCHK(c, hipMemcpy(tb_.p, b, n * b_words * 4, hipMemcpyHostToDevice));
+    }
+    const uint32_t *da = (const uint32_t*)ta.p, *db = (const uint32_t*)tb_.p;
+    uint32_t* dout = (uint32_t*)tout.p;
+#define MSM_G1_RAW(OP) msmk::k_test_g1_raw<OP><<<grid1(n, 64), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n)
+    switch (op) {
+        case MSM_OP_G1_RAW_MADD: MSM_G1_RAW(MSM_OP_G1_RAW_MADD); break;
+        case MSM_OP_G1_RAW_MADD_NEG_RAW: MSM_G1_RAW(MSM_OP_G1_RAW_MADD_NEG_RAW); break;
+        case MSM_OP_G1_RAW_MADD_M256: MSM_G1_RAW(MSM_OP_G1_RAW_MADD_M256); break;
+        case MSM_OP_G1_RAW_MADD_M256_NEG: MSM_G1_RAW(MSM_OP_G1_RAW_MADD_M256_NEG); break;
+        case MSM_OP_G1_RAW_ADD: MSM_G1_RAW(MSM_OP_G1_RAW_ADD); break;
+        case MSM_OP_G1_RAW_DBL: MSM_G1_RAW(MSM_OP_G1_RAW_DBL); break;
+        case MSM_OP_G1_RAW_ADD_WIDE_LDS: msmk::k_test_g1_raw_wide_lds<<<grid1(n, 8), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n); break;
+        default: msmk::k_test_g1_raw_wide_hbm<<<grid1(n, 8), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n); break;
+    }
+#undef MSM_G1_RAW
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(out, dout, n * a_words * 4, hipMemcpyDeviceToHost));
+    return MSM_OK;
+}
 int32_t msm_calibrate(msm_ctx* c, double* mad_per_s, double* fp_mul_per_s) {
     if (!c) return MSM_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -298,4 +298,55 @@ __global__ void __launch_bounds__(64) k_test_g2(const uint32_t* __restrict__ a, 
     store_xyzz2(out + (size_t)i * XW2, r);
 }
 
+// G1 group law on RAW limb records (msm_test_g1_raw_op), the counterpart of k_test_g2 for ec_bn254.hpp / ec_wide.hpp: a and out are XYZZ records as
+// store_xyzz writes them (36 words: X, Y, ZZ, ZZZ, 9 limbs each, internal domain, ANY representative within the header's bounds); the kernel loads
+// what the caller wrote, calls the one function and stores the limbs it got -- no conversion, no reduction.  One kernel per operation.
+// OP (MSM_OP_G1_RAW_* of include/msm_hip_testhooks.h): 0 xyzz_madd (b: 18 limbs x, y), 1 the same with fp_neg_raw<2> applied to the loaded y (what
+// k_accumulate_pieces<.., !M256> and fixed_base_bn254.hpp do for a negative digit: the raw limbs never cross the ABI), 2 / 3 xyzz_madd_m32 on
+// fp_unpack_shl5 of b's 16 words (any 32-bit values), plain / negated, 4 xyzz_add (b: 36 words), 5 xyzz_dbl
+template <uint32_t OP>
+__global__ void __launch_bounds__(64) k_test_g1_raw(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    xyzz r = load_xyzz(a + (size_t)i * XW);
+    if (OP == 0 || OP == 1) {
+        const uint32_t* bp = b + (size_t)i * 18;
+        affine q{load_coord(bp, 0), load_coord(bp, 1)};
+        if (OP == 1) q.y = fp_neg_raw<2>(q.y);
+        xyzz_madd(r, q);
+    } else if (OP == 2 || OP == 3) {
+        uint32_t wx[8], wy[8];
+        load_words8(wx, b + (size_t)i * 16);
+        load_words8(wy, b + (size_t)i * 16 + 8);
+        xyzz_madd_m32(r, fp_unpack_shl5(wx), fp_unpack_shl5(wy), OP == 3);
+    } else if (OP == 4) {
+        r = xyzz_add(r, load_xyzz(b + (size_t)i * XW));
+    } else {
+        r = xyzz_dbl(r);
+    }
+    store_xyzz(out + (size_t)i * XW, r);
+}
+// the eight-lane addition on raw records, as lds_tree_wide calls it: pair i belongs to the 8 lanes of group i, both records are staged in LDS by the
+// group's first lane and wide_add_records runs IN PLACE (out aliases a).  Geometry of k_test_g1_wide: 8 pairs per 64-lane workgroup.
+__global__ void __launch_bounds__(64) k_test_g1_raw_wide_lds(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out,
+                                                             uint32_t n) {
+    __shared__ uint32_t e[16 * XW];
+    const uint32_t g = threadIdx.x / WIDE_LANES, role = threadIdx.x % WIDE_LANES;
+    const uint32_t i = blockIdx.x * 8 + g;
+    if (i < n && role == 0) {
+        store_xyzz(e + (size_t)(2 * g) * XW, load_xyzz(a + (size_t)i * XW));
+        store_xyzz(e + (size_t)(2 * g + 1) * XW, load_xyzz(b + (size_t)i * XW));
+    }
+    __syncthreads();
+    if (i < n) wide_add_records(e + (size_t)(2 * g) * XW, e + (size_t)(2 * g + 1) * XW, e + (size_t)(2 * g) * XW);
+    __syncthreads();
+    if (i < n && role == 0) store_xyzz(out + (size_t)i * XW, load_xyzz(e + (size_t)(2 * g) * XW));
+}
+// the same on records in global memory with a distinct output, as k_pair_level_wide calls it
+__global__ void __launch_bounds__(64) k_test_g1_raw_wide_hbm(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out,
+                                                             uint32_t n) {
+    const uint32_t i = blockIdx.x * 8 + threadIdx.x / WIDE_LANES;
+    if (i < n) wide_add_records(a + (size_t)i * XW, b + (size_t)i * XW, out + (size_t)i * XW);
+}
+
 }  // namespace msmk

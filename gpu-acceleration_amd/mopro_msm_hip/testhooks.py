@@ -18,9 +18,14 @@ HOOK_SYMBOLS = [
     "msm_bn254_g1_generate_device", "msm_bn254_generate_scalars_host", "msm_test_fp_op", "msm_test_g1_op",
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
-    "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2", "msm_test_g2_op",
+    "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2", "msm_test_g2_op", "msm_test_g1_raw_op",
 ]
 OP_G2_MADD, OP_G2_ADD, OP_G2_DBL = 0, 1, 2  # MSM_OP_G2_* of include/msm_hip_testhooks.h
+# MSM_OP_G1_RAW_* of include/msm_hip_testhooks.h
+(OP_G1_RAW_MADD, OP_G1_RAW_MADD_NEG_RAW, OP_G1_RAW_MADD_M256, OP_G1_RAW_MADD_M256_NEG, OP_G1_RAW_ADD, OP_G1_RAW_DBL, OP_G1_RAW_ADD_WIDE_LDS,
+ OP_G1_RAW_ADD_WIDE_HBM) = range(8)
+G1_RAW_B_WORDS = {OP_G1_RAW_MADD: 18, OP_G1_RAW_MADD_NEG_RAW: 18, OP_G1_RAW_MADD_M256: 16, OP_G1_RAW_MADD_M256_NEG: 16, OP_G1_RAW_ADD: 36,
+                  OP_G1_RAW_DBL: 0, OP_G1_RAW_ADD_WIDE_LDS: 36, OP_G1_RAW_ADD_WIDE_HBM: 36}  # words per element of b
 _lib = None
 
 
@@ -44,6 +49,7 @@ def load_hooks_library():
     L.msm_test_g1_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_g2_sqrt.argtypes = [vp, _u32p, _u8p, _u32p, _u8p, C.c_size_t]
     L.msm_test_g2_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
+    L.msm_test_g1_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_decompose.argtypes = [vp, _u32p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32)]
     L.msm_test_abandon_after_sort.argtypes = [vp, _u32p, C.c_size_t]
     L.msm_calibrate.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -121,6 +127,25 @@ class HooksContext(MsmContext):
                 raise ValueError(f"a holds {a.shape[0]} records, b {b.shape[0]}")
         out = np.zeros_like(a)
         self._check(self._lib.msm_test_g2_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
+        return out
+
+    def test_g1_raw_op(self, op, a, b=None):
+        """the G1 group law on raw limb records (msm_test_g1_raw_op): a n x 36 limbs (X, Y, ZZ, ZZZ, 9 x 29-bit limbs each, internal domain, any
+        representative within the bounds of ec_bn254.hpp), b n x G1_RAW_B_WORDS[op] words (18 limbs x, y: the mixed additions; 16 words of any
+        value: the M256 ones; a second record: the additions; None: OP_G1_RAW_DBL) -> n x 36 limbs, exactly what the device stored"""
+        if op not in G1_RAW_B_WORDS:
+            raise ValueError(f"unknown raw G1 op {op}")
+        a = _words(a, 36)
+        if op == OP_G1_RAW_DBL:
+            b = None
+        else:  # the C hook reads n records of b: a missing or shorter b must not reach it
+            if b is None:
+                raise ValueError("every raw G1 op but OP_G1_RAW_DBL needs b")
+            b = _words(b, G1_RAW_B_WORDS[op])
+            if b.shape[0] != a.shape[0]:
+                raise ValueError(f"a holds {a.shape[0]} records, b {b.shape[0]}")
+        out = np.zeros_like(a)
+        self._check(self._lib.msm_test_g1_raw_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
         return out
 
     def ntt_set_tile_log2(self, tile_log2):

@@ -38,6 +38,22 @@ int32_t msm_test_fp_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint3
 #define MSM_OP_G1_MADD_M256 4u     /* as MADD, b's arkworks words gathered as they are (fp_unpack_shl5 + xyzz_madd_m32: k_accumulate_pieces<.., M256>) */
 #define MSM_OP_G1_MADD_M256_NEG 5u /* a - b by the same path (the digit's sign applied to S2) */
 int32_t msm_test_g1_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
+/* the G1 group law of csrc/ec_bn254.hpp / csrc/ec_wide.hpp on RAW limb records: n elements, no conversion and no reduction on the way in or out
+ * (msm_test_g1_op above only ever hands the law freshly reduced operands).  A record is 9 limbs of 29 bits per coordinate (one u32 word per limb,
+ * least significant first; value = sum limb_i * 2^(29 i)), internal Montgomery domain (x * 2^261 mod p, plus any multiple of p the bounds of
+ * ec_bn254.hpp allow: X < 7p, Y < 5p, ZZ, ZZZ < 2p; affine x < p, y < 2p).  XYZZ record: X Y ZZ ZZZ (36 words, the layout of store_xyzz); affine
+ * record: x y (18 words); the M256 operations take b as 16 words, x then y, ANY 32-bit values (the caller's R = 2^256 words as they are).  The
+ * identity is ZZ == 0 with every limb zero.  The caller picks the representative the device computes on and reads back exactly the limbs it stored.
+ * An input limb >= 2^29 is MSM_ERR_BAD_ARG (the 16-word b of the M256 operations is exempt); the bounds above are the caller's to keep. */
+#define MSM_OP_G1_RAW_MADD 0u          /* a: XYZZ record (36) + b: affine record (18) -> 36, xyzz_madd */
+#define MSM_OP_G1_RAW_MADD_NEG_RAW 1u  /* a - b: the kernel applies fp_neg_raw<2> to the y it loaded, then xyzz_madd (a negative digit in k_accumulate_pieces) */
+#define MSM_OP_G1_RAW_MADD_M256 2u     /* a: 36 + b: 16 words -> 36, xyzz_madd_m32 on fp_unpack_shl5 of the words */
+#define MSM_OP_G1_RAW_MADD_M256_NEG 3u /* a - b by the same path */
+#define MSM_OP_G1_RAW_ADD 4u           /* a: 36 + b: 36 -> 36, xyzz_add */
+#define MSM_OP_G1_RAW_DBL 5u           /* a: 36 -> 36, xyzz_dbl */
+#define MSM_OP_G1_RAW_ADD_WIDE_LDS 6u  /* as ADD by eight lanes per pair, records staged in LDS and added in place (lds_tree_wide's call) */
+#define MSM_OP_G1_RAW_ADD_WIDE_HBM 7u  /* as ADD by eight lanes per pair, records in global memory, distinct output (k_pair_level_wide's call) */
+int32_t msm_test_g1_raw_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
 /* the root-and-sign routine of k_g2_decompress on arbitrary Fq2 values (curve points whose y has a zero component cannot be constructed in closed
  * form: this is how the c1 = 0 / c0 = 0 branches of the sign rule get tested).  a_std: n x 16 standard-form words (c0, c1; canonical);
  * want_larger: n bytes (non-zero: the root that is the larger of (y, -y), see msm_bn254_g2_compress); out_std: n x 16 standard-form words of the
