@@ -392,6 +392,7 @@ struct PipeState {
     // k_accumulate_pieces' work items: a whole bucket of at most pmax entries, or a run of psplit entries of a longer one
     uint32_t pmax = 0, psplit = 0;
     size_t maxpieces = 0, maxpartials = 0;
+    bool flags_ready = false;  // flags_begin has run for this call: the decomposition of its first chunk must not clean the flag words again
 };
 
 // the counting-sort plan of ps (pipe_prepare keeps it in ps.sg); reads the decomposition and sort views only
@@ -517,6 +518,30 @@ void reduce_bufs(const msm_ctx* c, const PipeState& ps, uint32_t* rbuf[2], uint3
 // entries, and "fixed" when a test forces the lengths
 inline uint32_t split_arg(const msm_ctx* c, const PipeState& ps) { return msmk::psplit_arg(ps.psplit, c->knobs.split_shift, c->knobs.piece_len != 0); }
 
+// The flag words at the head of a call.  INVARIANT: when the first kernel of a call that can raise a bit in them is queued -- k_ark_repack (bit 16),
+// k_decompose* (bits 1-8) -- the words are zero and nothing queued before that kernel writes them again.  They clean themselves on the device (a
+// hipMemsetAsync is its own dispatch: ~5 us + a ~12 us bubble in front of it, per call and per streamed chunk): k_decompose zeroes the list counters of
+// the chunk, the kernel that ends an MSM zeroes the error and count words after copying them out, and finish_sync notes that (flags_clean).  Only a
+// context NOT known clean -- never used (the words are fresh hipMalloc memory), or left by a call that ended before finish_sync, possibly with bits
+// raised -- is zeroed from the host, ONCE per call and WAITED for: a stream-ordered memset behind a kernel of this call would erase that kernel's bit
+// (the repack of a struct array queued in front of the sort chain: the call then returned MSM_OK with the identity structs' (0, 0) words accumulated
+// as points), and one that is not waited for could be overtaken by a kernel of this call on the other stream.  A warm call pays one branch.
+// Two callers, never both in one call: flags_begin -- the host-pointer calls, before the first byte of the bases is queued (feed_bases /
+// launch_convert) -- which marks the call's PipeState, and enqueue_decompose(first) for the calls that reach it directly (device, resident, G2, the
+// hooks), which skips a marked state.  Both leave flags_clean false: from here on the words may hold bits until a finish_sync has taken them.
+int32_t flags_zero_if_unknown(msm_ctx* c, hipStream_t st) {
+    if (!c->flags_clean) {
+        HIPCHK(c, hipMemsetAsync(c->flags.p, 0, 64, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    c->flags_clean = false;
+    return MSM_OK;
+}
+int32_t flags_begin(msm_ctx* c, PipeState* ps, hipStream_t st) {  // (after pipe_prepare: it allocates the words)
+    ps->flags_ready = true;
+    return flags_zero_if_unknown(c, st);
+}
+
 // K1b: digits + signed recode of one (chunk of an) MSM on stream st (with the GLV split: two halves below 7 * 2^123 per scalar, 2*n_real digit
 // columns).  Needs the scalars (and the infinity mask), NOT the bases.  first = false: a later chunk of a streamed MSM (error bits and
 // the running count of additions survive).
@@ -534,14 +559,8 @@ int32_t enqueue_decompose(msm_ctx* c, const PipeState& ps, const uint8_t* d_inf,
     if (!sg.lds_counts && ps.tf > 1) return fail(c, MSM_ERR_BAD_ARG, "window_bits %u: the window table needs the LDS sort paths", cbits);
     if (!sg.lds_counts && (rc = ensure(c, c->ranks, pairs * 4))) return rc;
     if (!sg.lds_counts) HIPCHK(c, hipMemsetAsync(hist, 0, tb * 4, st));
-    // The flag words clean themselves (a hipMemsetAsync is its own dispatch: ~5 us + a ~12 us bubble in front of it, per call and per
-    // streamed chunk): k_decompose zeroes the list counters of the chunk, the kernel that ends an MSM zeroes the error and count
-    // words after copying them out.  Only a context whose last call did not complete (error paths) is cleaned from the host.
-    if (first && !c->flags_clean) {  // (error recovery only; waited for, so that no kernel of this call on the OTHER stream -- k_ark_repack raises an error bit -- can be overtaken by it)
-        HIPCHK(c, hipMemsetAsync(flags, 0, 64, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    if (first) c->flags_clean = false;
+    // (the flag words: see flags_zero_if_unknown -- a host-pointer call has been through flags_begin and may have queued its repack since)
+    if (first && !ps.flags_ready && (rc = flags_zero_if_unknown(c, st))) return rc;
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[EV_CONVERT], st));
     void* dg = c->digits.p;
     uint32_t *rk = (uint32_t*)c->ranks.p, *ph = (uint32_t*)c->phist.p, *pcu = (uint32_t*)c->pcursor.p;
@@ -1159,6 +1178,7 @@ int32_t run_single(msm_ctx* c, const HostInput& in, size_t n, uint32_t* out_jac,
     if ((rc = ensure(c, c->ibases, (glv ? 2 : 1) * n * 64))) return rc;
     if (in.carries_inf() && (rc = ensure(c, c->inf, n))) return rc;
     if ((rc = pipe_prepare(c, n, st, &ps))) return rc;
+    if ((rc = flags_begin(c, &ps, st))) return rc;  // before feed_bases: k_ark_repack raises its bit in front of the sort chain
     const bool overlap = n >= 4096 && !c->stage_timing;  // below that two cross-stream waits cost more than the copy
     hipStream_t bs = overlap ? cs : st;                  // stream the bases travel and are converted on
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[EV_START], st));
@@ -1235,6 +1255,7 @@ int32_t run_streamed(msm_ctx* c, const HostInput& in, size_t n, const std::vecto
     PrepareOpts po;
     po.plan_n = n;
     if ((rc = pipe_prepare(c, chunk, st, &ps, po))) return rc;  // workspace for the largest chunk before anything is in flight
+    if ((rc = flags_begin(c, &ps, st))) return rc;               // before the first launch_convert
     const PipeState ps_first = ps;                               // piece lengths: fixed by the largest chunk
     po.first = &ps_first;
     size_t lo = 0;

@@ -1,13 +1,19 @@
 """GPU parity tests (-m gpu): the HIP path, called through the C ABI, against the CPU oracle
 (oracle/bn254_oracle.c), the committed golden vectors, and size-independent properties at
 BASELINE.json's full sizes.  Bit-exact everywhere: this is integer work."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import mopro_msm_hip as mh
 from mopro_msm_hip import testhooks as th
-from conftest import golden_cases, load_golden, load_srs_sets, load_zkey_points
+from conftest import ROOT, golden_cases, load_golden, load_srs_sets, load_zkey_points
 from oracle import bn254_oracle as orc
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ark_cases import ark_image as _ark_image, fr_mont as _fr_mont  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 P, R = orc.P, orc.R_ORDER
@@ -807,29 +813,6 @@ def test_streamed_equals_single_shot_at_2_pow_18(ctx, hk):
 
 
 # ---- zero-copy arkworks ingestion -------------------------------------------
-def _ark_image(bases_std, inf, stride, x_off, y_off, inf_off, rng):
-    """byte image of a [G1Affine] slice: Fq Montgomery limbs at x_off / y_off, `infinity` bool at inf_off, garbage in
-    the padding (arkworks' identity is x = y = 0, infinity = true)"""
-    n = bases_std.shape[0]
-    img = rng.integers(0, 256, size=(n, stride), dtype=np.uint8)
-    R = 1 << 256
-    for i in range(n):
-        x = orc.words_to_int(bases_std[i, :8]) * R % P
-        y = orc.words_to_int(bases_std[i, 8:]) * R % P
-        if inf is not None and inf[i]:
-            x = y = 0
-        img[i, x_off:x_off + 32] = np.frombuffer(x.to_bytes(32, "little"), np.uint8)
-        img[i, y_off:y_off + 32] = np.frombuffer(y.to_bytes(32, "little"), np.uint8)
-        if inf_off is not None:
-            img[i, inf_off] = 1 if (inf is not None and inf[i]) else 0
-    return img
-
-
-def _fr_mont(scalars):
-    R = 1 << 256
-    return np.stack([orc.int_to_words(orc.words_to_int(s) * R % orc.R_ORDER) for s in scalars])
-
-
 @pytest.mark.parametrize("layout", [(72, 0, 32, 64), (80, 40, 8, 72), (64, 32, 0, None)])
 def test_arkworks_struct_ingestion(ctx, layout):
     stride, x_off, y_off, inf_off = layout
