@@ -7,7 +7,11 @@
 // R = 2^256 Montgomery words in or out, 1/n, coset powers) is ONE multiplication by a constant the host prepares.
 //
 // Value discipline: NORMALISED = all nine limbs < 2^29 (so the value is < 2^261 ~ 169 r).
-//   fr_mul     inputs normalised; output normalised, value < A*B/2^261 + r.  Column bound: 9*2^58 + 9*2^58 + carry < 2^63.
+//   fr_mul     inputs normalised AND A*B < (2^261 - r) * 2^261; output normalised, value < A*B/2^261 + r.  Normalised operands alone are NOT
+//              enough: the result is (A*B + m*r) / 2^261 with m up to 2^261 - 1, so (2^261 - 1)^2 gives about 169.86 r >= 2^261 (169.28 r) and
+//              the top limb leaves 29 bits (asserted below; tools/fr_bounds_check.cpp holds the case).  Sufficient forms, the ones the code uses:
+//              both operands < 168.78 r; or one operand <= 2^261 - r (~168.28 r: anything < 168 r, a canonical or < 2r table entry, any 256-bit
+//              word < 5.3 r) and the other merely normalised.  Column bound: 9*2^58 + 9*2^58 + carry < 2^63.
 //              With one operand < 2r (canonical table entries are < r) and the other < 2^261: output < 2r + r = 3r; with the other < 84r: < 2r.
 //   fr_add     limb-wise + ripple; the sum must stay < 2^261 (asserted on the top limb)
 //   fr_sub<K>  A + K*r - B; B normalised and B < (K-1)*r
@@ -166,7 +170,8 @@ __host__ __device__ inline fr fr_pow_u32(const fr& a, uint32_t e) {
     }
     return acc;
 }
-// a^(r-2) (Fermat); a != 0 mod r (0 gives 0)
+// a^(r-2) (Fermat); a: rep, normalised, < 84r as fr_pow_u32 (the squares fall 84r -> 42.7r -> 11.8r -> < 2r, every product has a factor < 2r);
+// result < 2r; a != 0 mod r (0 gives 0)
 __host__ __device__ inline fr fr_inv(const fr& a) {
     fr acc = fr_one(), b = a;
     for (int i = 0; i < 254; i++) {

@@ -19,6 +19,9 @@
 //   on the way down   ni = inv * prefix < 2 * 2 / 169 + 1 < 2: fr_reduce_lt2r gives the canonical output;  inv * u < 2
 //   a power walk      cur < 2, the stride's power < 2:  cur * step < 2
 //   lincomb           three products word * rep(k) < 5.3 * 2 / 169 + 1 < 2 each, their sum < 6, times the canonical post < 6 / 169 + 1 < 2
+//   host arguments    (frv_*_args, frv_pow_u64) every factor is a constant of ntt_consts(), an fr_from_std, an fr_inv / fr_pow_u32 result or a
+//                     product of two such: < 2, so every product is < 2 * 2 / 169 + 1 < 2 and every fr_sub<3> has a subtrahend < 2
+// No operand of an fr_mul here exceeds 5.3: fr_mul's precondition A * B < (2^261 - r) * 2^261 (fr_bn254.hpp) holds with room everywhere.
 #pragma once
 #include "ntt_bn254.hpp"
 

@@ -67,7 +67,7 @@ int32_t ntt_two_level(msm_ctx* c, DevBuf& buf, const nttk::fr& base, const nttk:
     int32_t rc = ensure(c, buf, ((size_t)nlo + nhi) * 32);
     if (rc) return rc;
     nttk::fr bh = base;
-    for (uint32_t i = 0; i < h; i++) bh = nttk::fr_mul(bh, bh);
+    for (uint32_t i = 0; i < h; i++) bh = nttk::fr_mul(bh, bh);  // base < 2r (a root, a coset generator or the inverse of one): every square < 2r
     ntt_pow_table(base, scale, nlo, (uint32_t*)buf.p, st);
     ntt_pow_table(bh, nttk::fr_one(), nhi, (uint32_t*)buf.p + (size_t)nlo * 8, st);
     HIPCHK(c, hipGetLastError());
@@ -233,7 +233,7 @@ int32_t msm_bn254_fr_mul_sub_scale_device(msm_ctx* c, const void* d_a, const voi
     const bool im = flags & MSM_NTT_IN_MONT, om = flags & MSM_NTT_OUT_MONT;
     const fr pre = ntt_factor_in(flags);
     fr post = k_std ? fr_from_std(k_std) : fr_one();
-    if (om && !im) post = fr_mul(post, ntt_consts().p256);
+    if (om && !im) post = fr_mul(post, ntt_consts().p256);  // post < 2r (fr_from_std) or < r, the constant < 2r: the product < 2r
     if (im && !om) post = fr_mul(post, ntt_consts().m256);
     post = fr_canonical(post);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;

@@ -192,6 +192,58 @@ int32_t msm_test_g1_raw_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uin
     HIPCHK(c, hipMemcpy(out, dout, n * a_words * 4, hipMemcpyDeviceToHost));
     return MSM_OK;
 }
+// the scalar field on raw limb records (msmk::k_test_fr_raw): checks, alloc / copy / launch / sync as msm_test_g1_raw_op
+int32_t msm_test_fr_raw_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+    if (!c || !a || !out) return MSM_ERR_BAD_ARG;
+    if (op > MSM_OP_FR_RAW_INV) return fail(c, MSM_ERR_BAD_ARG, "unknown raw Fr op %u", op);
+    const bool b_limbs = op <= MSM_OP_FR_RAW_SUB8, b_read = b_limbs || op == MSM_OP_FR_RAW_POW_U32;
+    if (b_read && !b) return MSM_ERR_BAD_ARG;
+    if (n == 0) return MSM_ERR_EMPTY;
+    if (n > 0x7FFFFFFFull / 9) return fail(c, MSM_ERR_BAD_ARG, "n too large");
+    // a limb of 2^29 or more could overflow a column accumulator of the multiplication: a malformed test is refused, not run
+    // (fr_normalize exists for such limbs, and the 8 words of fr_unpack / fr_from_std are not limbs: any 256 bits)
+    const bool a_limbs = op != MSM_OP_FR_RAW_NORMALIZE && op != MSM_OP_FR_RAW_UNPACK && op != MSM_OP_FR_RAW_FROM_STD;
+    for (size_t i = 0; a_limbs && i < n * 9; i++)
+        if (a[i] > bn254::FP_MASK) return fail(c, MSM_ERR_BAD_ARG, "a: word %zu of record %zu is not a 29-bit limb", i % 9, i / 9);
+    for (size_t i = 0; b_limbs && i < n * 9; i++)
+        if (b[i] > bn254::FP_MASK) return fail(c, MSM_ERR_BAD_ARG, "b: word %zu of record %zu is not a 29-bit limb", i % 9, i / 9);
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    DevTmp ta, tb_, tout;  // freed on every exit path
+    HIPCHK(c, hipMalloc(&ta.p, n * 36));
+    HIPCHK(c, hipMalloc(&tout.p, n * 36));
+    HIPCHK(c, hipMemcpy(ta.p, a, n * 36, hipMemcpyHostToDevice));
+    if (b_read) {
+        HIPCHK(c, hipMalloc(&tb_.p, n * 36));
+        HIPCHK(c, hipMemcpy(tb_.p, b, n * 36, hipMemcpyHostToDevice));
+    }
+    const uint32_t *da = (const uint32_t*)ta.p, *db = (const uint32_t*)tb_.p;
+    uint32_t* dout = (uint32_t*)tout.p;
+#define MSM_FR_RAW(OP) \
+    case OP: msmk::k_test_fr_raw<OP><<<grid1(n, 64), 64, 0, c->stream>>>(da, db, dout, (uint32_t)n); break
+    switch (op) {
+        MSM_FR_RAW(MSM_OP_FR_RAW_MUL);
+        MSM_FR_RAW(MSM_OP_FR_RAW_ADD);
+        MSM_FR_RAW(MSM_OP_FR_RAW_SUB2);
+        MSM_FR_RAW(MSM_OP_FR_RAW_SUB3);
+        MSM_FR_RAW(MSM_OP_FR_RAW_SUB7);
+        MSM_FR_RAW(MSM_OP_FR_RAW_SUB8);
+        MSM_FR_RAW(MSM_OP_FR_RAW_NORMALIZE);
+        MSM_FR_RAW(MSM_OP_FR_RAW_REDUCE_LT2R);
+        MSM_FR_RAW(MSM_OP_FR_RAW_CANONICAL);
+        MSM_FR_RAW(MSM_OP_FR_RAW_UNPACK);
+        MSM_FR_RAW(MSM_OP_FR_RAW_PACK);
+        MSM_FR_RAW(MSM_OP_FR_RAW_FROM_STD);
+        MSM_FR_RAW(MSM_OP_FR_RAW_TO_STD);
+        MSM_FR_RAW(MSM_OP_FR_RAW_POW_U32);
+        MSM_FR_RAW(MSM_OP_FR_RAW_INV);
+    }
+#undef MSM_FR_RAW
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(out, dout, n * 36, hipMemcpyDeviceToHost));
+    return MSM_OK;
+}
 int32_t msm_calibrate(msm_ctx* c, double* mad_per_s, double* fp_mul_per_s) {
     if (!c) return MSM_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -6,6 +6,8 @@
 #pragma once
 #include "msm_kernels.hpp"
 #include "msm_kernels_g2.hpp"
+#include "fr_bn254.hpp"
+#include "../../include/msm_hip_testhooks.h"  // MSM_OP_FR_RAW_*
 
 namespace msmk {
 
@@ -347,6 +349,61 @@ __global__ void __launch_bounds__(64) k_test_g1_raw_wide_hbm(const uint32_t* __r
                                                              uint32_t n) {
     const uint32_t i = blockIdx.x * 8 + threadIdx.x / WIDE_LANES;
     if (i < n) wide_add_records(a + (size_t)i * XW, b + (size_t)i * XW, out + (size_t)i * XW);
+}
+
+// the scalar field Fr of fr_bn254.hpp on RAW limb records (msm_test_fr_raw_op), the counterpart of k_test_g1_raw one level down: a, b and out are
+// n x 9 words; one lane per element loads the nine words the caller wrote, calls the one function and stores the nine limbs it got -- no conversion,
+// no reduction.  Where the function reads or writes 8 words (unpack, from_std; pack, to_std) word 8 is not read / is stored as 0.  One kernel per
+// operation.  OP: MSM_OP_FR_RAW_* of include/msm_hip_testhooks.h
+template <uint32_t OP>
+__global__ void __launch_bounds__(64) k_test_fr_raw(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out, uint32_t n) {
+    using namespace bn254;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* ap = a + (size_t)i * 9;
+    uint32_t* op = out + (size_t)i * 9;
+    fr x, r;
+    if (OP == MSM_OP_FR_RAW_UNPACK || OP == MSM_OP_FR_RAW_FROM_STD) {
+        uint32_t w[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) w[k] = ap[k];
+        r = OP == MSM_OP_FR_RAW_UNPACK ? fr_unpack(w) : fr_from_std(w);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; k++) x.v[k] = ap[k];
+    }
+    if (OP <= MSM_OP_FR_RAW_SUB8) {
+        fr y;
+#pragma unroll
+        for (int k = 0; k < 9; k++) y.v[k] = b[(size_t)i * 9 + k];
+        if (OP == MSM_OP_FR_RAW_MUL) r = fr_mul(x, y);
+        else if (OP == MSM_OP_FR_RAW_ADD) r = fr_add(x, y);
+        else if (OP == MSM_OP_FR_RAW_SUB2) r = fr_sub<2>(x, y);
+        else if (OP == MSM_OP_FR_RAW_SUB3) r = fr_sub<3>(x, y);
+        else if (OP == MSM_OP_FR_RAW_SUB7) r = fr_sub<7>(x, y);
+        else r = fr_sub<8>(x, y);
+    } else if (OP == MSM_OP_FR_RAW_NORMALIZE) {
+        r = fr_normalize(x);
+    } else if (OP == MSM_OP_FR_RAW_REDUCE_LT2R) {
+        r = fr_reduce_lt2r(x);
+    } else if (OP == MSM_OP_FR_RAW_CANONICAL) {
+        r = fr_canonical(x);
+    } else if (OP == MSM_OP_FR_RAW_POW_U32) {
+        r = fr_pow_u32(x, b[(size_t)i * 9]);
+    } else if (OP == MSM_OP_FR_RAW_INV) {
+        r = fr_inv(x);
+    }
+    if (OP == MSM_OP_FR_RAW_PACK || OP == MSM_OP_FR_RAW_TO_STD) {
+        uint32_t w[8];
+        if (OP == MSM_OP_FR_RAW_PACK) fr_pack(w, x);
+        else fr_to_std(w, x);
+#pragma unroll
+        for (int k = 0; k < 8; k++) op[k] = w[k];
+        op[8] = 0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; k++) op[k] = r.v[k];
+    }
 }
 
 }  // namespace msmk

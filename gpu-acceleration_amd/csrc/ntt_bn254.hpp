@@ -161,7 +161,9 @@ NTT_HD void ntt_phase_load(const NttPass& ps, const NttTables& tb, const uint32_
     ntt_lds_put(lds, slot, a);
 }
 
-// ---- phase 2: level s (rows a and a + 2^s), work item wi < 2^(T-1).  Values entering level s are < (2 + 3s) r.
+// ---- phase 2: level s (rows a and a + 2^s), work item wi < 2^(T-1).  Values entering level s are < (2 + 3s) r: u + x < (2 + 3s) r + 2r and
+// u + 3r - x < (2 + 3s) r + 3r.  s <= 9 here (twelve levels would end below 38r): rows stay far below 2^261 - r ~ 168.28 r, where fr_mul's precondition
+// A * B < (2^261 - r) * 2^261 holds against any normalised factor (tests/test_gpu_22_fr_ops.py runs twelve levels on the device)
 template <uint32_t T>
 NTT_HD void ntt_phase_butterfly(const NttPass& ps, const NttTables& tb, uint32_t s, uint32_t wi, uint32_t* lds) {
     const uint32_t c = T - ps.t, col = wi & ((1u << c) - 1u), bf = wi >> c;
@@ -249,7 +251,7 @@ inline fr ntt_factor_in(uint32_t flags) { return flags & NTT_F_IN_MONT ? ntt_con
 // rep(x) times this gives the output words as raw limbs: rep(s * 2^-261) resp. rep(s * 2^-5), s = 1/n for an inverse transform
 inline fr ntt_factor_out(uint32_t k, uint32_t flags) {
     fr f = flags & NTT_F_OUT_MONT ? ntt_consts().m5 : ntt_consts().m261;
-    if (flags & NTT_F_INVERSE) f = fr_mul(f, fr_pow_u32(ntt_consts().inv2, k));
+    if (flags & NTT_F_INVERSE) f = fr_mul(f, fr_pow_u32(ntt_consts().inv2, k));  // both fr_inv / fr_pow_u32 results, < 2r: the product < 2r
     return f;
 }
 inline uint32_t ntt_split(uint32_t k) { return (k + 1) / 2; }  // low-level bits of a two-level table over k-bit exponents

@@ -95,7 +95,8 @@ NTT_HD void r1cs_item(const R1csView& v, uint32_t item, const uint32_t* wit, con
     }
     (void)bound;
     const bool partial = it.y & R1CS_ITEM_PARTIAL;
-    // acc < 168 r, the factor < r: product < 168 r * r / 2^261 + r < 2 r
+    // acc < 168 r, the factor < r: product < 168 r * r / 2^261 + r < 2 r.  (fr_mul needs A * B < (2^261 - r) * 2^261: 168 r < 2^261 - r ~ 168.28 r,
+    // so this accumulator is inside it against ANY normalised factor -- R1CS_ACC_MAX_R may not grow past 168)
     uint32_t w8[8];
     fr_pack(w8, fr_reduce_lt2r(fr_mul(acc, partial ? fr_one() : post)));
     ntt_store8((partial ? partials : out) + (size_t)it.x * 8, w8);

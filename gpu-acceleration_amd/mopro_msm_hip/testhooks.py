@@ -19,6 +19,7 @@ HOOK_SYMBOLS = [
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
     "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2", "msm_test_g2_op", "msm_test_g1_raw_op",
+    "msm_test_fr_raw_op",
 ]
 OP_G2_MADD, OP_G2_ADD, OP_G2_DBL = 0, 1, 2  # MSM_OP_G2_* of include/msm_hip_testhooks.h
 # MSM_OP_G1_RAW_* of include/msm_hip_testhooks.h
@@ -26,6 +27,12 @@ OP_G2_MADD, OP_G2_ADD, OP_G2_DBL = 0, 1, 2  # MSM_OP_G2_* of include/msm_hip_tes
  OP_G1_RAW_ADD_WIDE_HBM) = range(8)
 G1_RAW_B_WORDS = {OP_G1_RAW_MADD: 18, OP_G1_RAW_MADD_NEG_RAW: 18, OP_G1_RAW_MADD_M256: 16, OP_G1_RAW_MADD_M256_NEG: 16, OP_G1_RAW_ADD: 36,
                   OP_G1_RAW_DBL: 0, OP_G1_RAW_ADD_WIDE_LDS: 36, OP_G1_RAW_ADD_WIDE_HBM: 36}  # words per element of b
+# MSM_OP_FR_RAW_* of include/msm_hip_testhooks.h
+FR_RAW_OPS = ("MUL", "ADD", "SUB2", "SUB3", "SUB7", "SUB8", "NORMALIZE", "REDUCE_LT2R", "CANONICAL", "UNPACK", "PACK", "FROM_STD", "TO_STD", "POW_U32",
+              "INV")
+(OP_FR_RAW_MUL, OP_FR_RAW_ADD, OP_FR_RAW_SUB2, OP_FR_RAW_SUB3, OP_FR_RAW_SUB7, OP_FR_RAW_SUB8, OP_FR_RAW_NORMALIZE, OP_FR_RAW_REDUCE_LT2R,
+ OP_FR_RAW_CANONICAL, OP_FR_RAW_UNPACK, OP_FR_RAW_PACK, OP_FR_RAW_FROM_STD, OP_FR_RAW_TO_STD, OP_FR_RAW_POW_U32, OP_FR_RAW_INV) = range(15)
+FR_RAW_NEEDS_B = (OP_FR_RAW_MUL, OP_FR_RAW_ADD, OP_FR_RAW_SUB2, OP_FR_RAW_SUB3, OP_FR_RAW_SUB7, OP_FR_RAW_SUB8, OP_FR_RAW_POW_U32)
 _lib = None
 
 
@@ -50,6 +57,7 @@ def load_hooks_library():
     L.msm_test_g2_sqrt.argtypes = [vp, _u32p, _u8p, _u32p, _u8p, C.c_size_t]
     L.msm_test_g2_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_g1_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
+    L.msm_test_fr_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_decompose.argtypes = [vp, _u32p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32)]
     L.msm_test_abandon_after_sort.argtypes = [vp, _u32p, C.c_size_t]
     L.msm_calibrate.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -146,6 +154,26 @@ class HooksContext(MsmContext):
                 raise ValueError(f"a holds {a.shape[0]} records, b {b.shape[0]}")
         out = np.zeros_like(a)
         self._check(self._lib.msm_test_g1_raw_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
+        return out
+
+    def test_fr_raw_op(self, op, a, b=None):
+        """the scalar field on raw limb records (msm_test_fr_raw_op): a n x 9 words (9 x 29-bit limbs, any representative fr_bn254.hpp allows for
+        the operation; the 8 words of a 256-bit pattern and an ignored ninth for OP_FR_RAW_UNPACK / _FROM_STD), b n x 9 words for the operations of
+        FR_RAW_NEEDS_B (a second record; OP_FR_RAW_POW_U32: the exponent in b[i][0]) -> n x 9 words, exactly what the device stored (word 8 is 0
+        where the function writes 8 words: OP_FR_RAW_PACK / _TO_STD)"""
+        if op not in range(len(FR_RAW_OPS)):
+            raise ValueError(f"unknown raw Fr op {op}")
+        a = _words(a, 9)
+        if op not in FR_RAW_NEEDS_B:
+            b = None
+        else:  # the C hook reads n records of b: a missing or shorter b must not reach it
+            if b is None:
+                raise ValueError("MUL, ADD, SUB<K> and POW_U32 need b")
+            b = _words(b, 9)
+            if b.shape[0] != a.shape[0]:
+                raise ValueError(f"a holds {a.shape[0]} records, b {b.shape[0]}")
+        out = np.zeros_like(a)
+        self._check(self._lib.msm_test_fr_raw_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
         return out
 
     def ntt_set_tile_log2(self, tile_log2):

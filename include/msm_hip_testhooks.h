@@ -69,6 +69,29 @@ int32_t msm_test_g2_sqrt(msm_ctx *ctx, const uint32_t *a_std, const uint8_t *wan
 #define MSM_OP_G2_ADD 1u  /* a: 72 + b: 72 -> 72 */
 #define MSM_OP_G2_DBL 2u  /* a: 72 -> 72 */
 int32_t msm_test_g2_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
+/* the scalar field Fr of csrc/fr_bn254.hpp on RAW limb records: n elements, one device lane each, no conversion and no reduction on the way in or
+ * out.  a, b and out hold n x 9 words: 9 limbs of 29 bits (one u32 word per limb, least significant first; value = sum limb_i * 2^(29 i)), ANY
+ * representative the value discipline of fr_bn254.hpp allows for the operation.  Where a function reads or writes 8 words (32-bit words of a
+ * 256-bit pattern), word 8 is ignored on input and written as 0 on output.  b is read by MUL, ADD, SUB<K> (a second record) and POW_U32 (the
+ * exponent in b[i][0], words 1..8 ignored); the other operations take b == NULL.  The caller picks the representative the device computes on and
+ * reads back exactly the limbs it stored.  A limb >= 2^29 in an operand that must be normalised is MSM_ERR_BAD_ARG (a of NORMALIZE, UNPACK and
+ * FROM_STD takes any 32-bit words); the value bounds are the caller's to keep: the device asserts nothing. */
+#define MSM_OP_FR_RAW_MUL 0u          /* fr_mul(a, b): a * b * 2^-261, needs a * b < (2^261 - r) * 2^261 */
+#define MSM_OP_FR_RAW_ADD 1u          /* fr_add(a, b): a + b < 2^261 */
+#define MSM_OP_FR_RAW_SUB2 2u         /* fr_sub<2>(a, b): a + 2r - b, b < r */
+#define MSM_OP_FR_RAW_SUB3 3u         /* fr_sub<3>: b < 2r (the butterflies) */
+#define MSM_OP_FR_RAW_SUB7 4u         /* fr_sub<7>: b < 6r */
+#define MSM_OP_FR_RAW_SUB8 5u         /* fr_sub<8>: b < 7r, the last row of the pad table */
+#define MSM_OP_FR_RAW_NORMALIZE 6u    /* fr_normalize(a): limbs 0..7 + carry < 2^32, value < 2^261 */
+#define MSM_OP_FR_RAW_REDUCE_LT2R 7u  /* fr_reduce_lt2r(a): a < 2r */
+#define MSM_OP_FR_RAW_CANONICAL 8u    /* fr_canonical(a): any normalised a */
+#define MSM_OP_FR_RAW_UNPACK 9u       /* fr_unpack(a[0..7]) */
+#define MSM_OP_FR_RAW_PACK 10u        /* fr_pack(out[0..7], a): a < 2^256 */
+#define MSM_OP_FR_RAW_FROM_STD 11u    /* fr_from_std(a[0..7]) */
+#define MSM_OP_FR_RAW_TO_STD 12u      /* fr_to_std(out[0..7], a): any normalised a */
+#define MSM_OP_FR_RAW_POW_U32 13u     /* fr_pow_u32(a, b[0]): a < 84r */
+#define MSM_OP_FR_RAW_INV 14u         /* fr_inv(a): a < 84r */
+int32_t msm_test_fr_raw_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
 /* signed/unsigned digit decomposition of the planner's choice, digits[w*n + i] as int32 */
 int32_t msm_test_decompose(msm_ctx *ctx, const uint32_t *scalars, size_t n, uint32_t window_bits, int32_t *digits);
 
