@@ -6,12 +6,11 @@ a + i d); nothing here touches the code under test.
 
 Every builder returns (bases n x 32 words in the requested form, scalars n x 8 words, inf mask or None, expected affine point or None).
 Shapes: tiled, opposite, scalar_opposite, endo_triple, one_base_ramp, with_mask over any of them, and the seeded net of net_case.
-The bookkeeping at the end (unsigned_bucket_sizes, expected_lists) says which list of the combine kernel a bucket of a given size reaches
-under a forced piece length: the rule of the piece plan written down once more, in Python integers."""
+The bookkeeping (unsigned_bucket_sizes, expected_lists: which list of the combine kernel a bucket of a given size reaches under a forced piece
+length), the scalars and the index logic of an instance are shared with the G1 module: tools/msm_cases_common.py."""
 import os
 import random
 import sys
-from collections import Counter
 
 import numpy as np
 
@@ -20,7 +19,11 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import bn254_g2_py as g2  # noqa: E402
 import fixed_base_g2_cases as fb2  # noqa: E402
+import msm_cases_common as common  # noqa: E402
 from g2_pointwise_mul_cases import point_array  # noqa: E402
+# (shared with tools/g1_msm_cases.py: the scalars, the bucket sizes of a plain plan and the piece rule)
+from msm_cases_common import (LONG_SEG, LONG_SPAN, SPREAD_BITS, expected_lists, scalar_words, seeded_scalars, spread_scalars,  # noqa: E402,F401
+                              unsigned_bucket_sizes)
 
 P, R = g2.P, g2.R
 FORM_STD, FORM_MONT = 0, 1
@@ -45,10 +48,6 @@ def phi2(pt):
     return None if pt is None else (g2.smul2(pt[0], BETA2), pt[1])
 
 
-def scalar_words(vs):
-    return np.array([g2.int_words(v) for v in vs], np.uint32).reshape(len(vs), 8)
-
-
 def decode(bases, form):
     """the affine points of n x 32 emitted words (an all-zero record: None)"""
     ri = pow(g2.R256, -1, P)
@@ -61,42 +60,14 @@ def decode(bases, form):
     return out
 
 
-class Instance:
-    """rows (point upts[pidx[i]] of logarithm ulogs[pidx[i]], scalar uscal[sidx[i]]), row i masked as infinity where inf[i]; zeroed[i]: the
-    masked row's base words are zeros instead of the point's"""
+class Instance(common.Instance):
+    """common.Instance over G2: the points are affine pairs of Fq2 pairs, the expected value one product by the independent law"""
 
-    def __init__(self, ulogs, upts, pidx, uscal, sidx, inf=None, zeroed=None):
-        self.ulogs, self.upts, self.uscal = [c % R for c in ulogs], list(upts), [s % R for s in uscal]
-        self.pidx, self.sidx = np.asarray(pidx, np.int64), np.asarray(sidx, np.int64)
-        assert len(self.pidx) == len(self.sidx) and len(self.ulogs) == len(self.upts)
-        self.inf = None if inf is None else np.asarray(inf, np.uint8)
-        self.zeroed = zeroed
-        self._expected = None
+    def point_words(self, form):
+        return point_array(self.upts, form)
 
-    @property
-    def n(self):
-        return len(self.pidx)
-
-    def scalars(self):
-        return [self.uscal[j] for j in self.sidx.tolist()]
-
-    def logs(self):
-        return [self.ulogs[j] for j in self.pidx.tolist()]
-
-    def total(self):
-        live = [True] * self.n if self.inf is None else [not m for m in self.inf.tolist()]
-        return sum(self.uscal[s] * self.ulogs[p] for p, s, ok in zip(self.pidx.tolist(), self.sidx.tolist(), live) if ok) % R
-
-    def expected(self):
-        if self._expected is None:
-            self._expected = (g2.mul(GEN, self.total()),)  # (None for 0; one scalar multiplication, made once)
-        return self._expected[0]
-
-    def emit(self, form=FORM_MONT):
-        bases = np.ascontiguousarray(point_array(self.upts, form)[self.pidx])
-        if self.zeroed is not None:
-            bases[np.asarray(self.zeroed, bool)] = 0
-        return bases, np.ascontiguousarray(scalar_words(self.uscal)[self.sidx]), self.inf, self.expected()
+    def product(self, total):
+        return g2.mul(GEN, total)
 
 
 def base_points(L, seed):
@@ -111,25 +82,6 @@ def base_points(L, seed):
         return logs, fb2.points(logs)
     a, d = rnd.randrange(1, R), rnd.randrange(1, 1 << 64)
     return [(a + i * d) % R for i in range(L)], g2.chain_points(a, d, L)
-
-
-def seeded_scalars(seed, count):
-    rnd = random.Random(seed ^ 0x5CA1A25)
-    return [rnd.randrange(1, R) for _ in range(count)]
-
-
-SPREAD_BITS = 234  # 254 - 20: below the top window of every window width the planner accepts
-
-
-def spread_scalars(seed):
-    """three scalars below 2^234 whose pairwise differences (XOR) have no two neighbouring zero bits below bit 234: s, s ^ 0101..., s ^ 1010...
-    (bit 233 of s is zero).  Cut into windows of any width from 2 to 20 with plain digits, no two of them share a nonzero digit in any window, and
-    the top window (the bits from c (W - 1) >= 234 on, whose entries the plan spreads over its buckets by point index) stays empty: every
-    non-empty bucket of an instance tiled from them holds exactly T entries, whatever width the planner picks."""
-    s = random.Random(seed ^ 0x5B8EAD).getrandbits(SPREAD_BITS - 1)
-    m1 = sum(1 << b for b in range(0, SPREAD_BITS, 2))
-    m2 = sum(1 << b for b in range(1, SPREAD_BITS, 2))
-    return [s, s ^ m1, s ^ m2]
 
 
 # ---- the shapes: raw_*() return an Instance, the functions of the same name without the prefix emit it -------------------------------------
@@ -192,24 +144,7 @@ def raw_one_base_ramp(m, c, sign="same", log=RAMP_LOG):
 def raw_with_mask(inst, seed):
     """`inst` with about a quarter of its rows masked as infinity (every other one of them with zeroed base words, as a caller that keeps no
     coordinates for such a point would pass them) and about a sixth carrying the scalar 0; at least one row of each kind, and one row left alone"""
-    rnd = random.Random(seed ^ 0x3A5C)
-    n = inst.n
-    assert n >= 3
-    inf, sidx = np.zeros(n, np.uint8), inst.sidx.copy()
-    uscal = inst.uscal + [0]
-    for i in range(n):
-        u = rnd.random()
-        if u < 0.25:
-            inf[i] = 1
-        elif u < 0.42:
-            sidx[i] = len(uscal) - 1
-    order = rnd.sample(range(n), 3)
-    inf[order[0]], inf[order[1]], inf[order[2]] = 1, 0, 0
-    sidx[order[1]] = len(uscal) - 1
-    sidx[order[2]] = inst.sidx[order[2]]
-    masked = np.flatnonzero(inf)
-    zeroed = np.zeros(n, bool)
-    zeroed[masked[::2]] = True
+    inf, zeroed, uscal, sidx = common.mask_rows(inst, seed)
     return Instance(inst.ulogs, inst.upts, inst.pidx, uscal, sidx, inf, zeroed)
 
 
@@ -240,7 +175,7 @@ def with_mask(inst, seed, form=FORM_MONT):
 # ---- the seeded net: 40 combinations of size, bases, scalars, mask, window width, digit flags and forced piece length ------------------------
 NET_SEED, NET_CASES, NET_CHAIN = 20261019, 40, 4096
 NET_A, NET_D = 0x6F3B2A1908F7E6D5C4B3A29180F7E6D5C4B3A291, 0x9E3779B97F4A7C15
-FLAG_UNSIGNED_DIGITS, FLAG_NO_GLV = 1, 2  # MSM_FLAG_* of include/msm_hip.h
+FLAG_UNSIGNED_DIGITS, FLAG_NO_GLV = common.FLAG_UNSIGNED_DIGITS, common.FLAG_NO_GLV  # MSM_FLAG_* of include/msm_hip.h
 BASE_MODES = ("distinct", "odd rows = row 0", "every third negated", "all equal")
 SCALAR_MODES = ("uniform", "all equal", "three distinct", "below 2^32", "60 % zeros", "all r - 1")
 _CHAIN = []
@@ -290,45 +225,3 @@ def net_case(it, n=None):
                  piece_len=[None, "1", "2", "7"][int(rng.integers(0, 4))])
     idx = np.arange(n)
     return combo, Instance(logs, pts, idx, sc, idx, inf)
-
-
-# ---- which list a bucket reaches --------------------------------------------------------------------------------------------------------------
-LONG_SPAN, LONG_SEG = 8, 1024  # pieces from which a bucket is folded by workgroups; pieces per workgroup (one segment)
-
-
-def unsigned_bucket_sizes(scalars, inf, window_bits, scalar_bits=254):
-    """entries per non-empty bucket of an unsplit plan with plain digits: digit w of s is (s >> (w * c)) & (2^c - 1), a zero digit and a masked
-    row give no entry.  A Counter {(window, digit): entries}.  The TOP window's entries are spread over its buckets by point index (msm_plan_t
-    top_digit_bits): instances whose buckets are counted leave it empty (spread_scalars, one_base_ramp), anything else is a ValueError."""
-    c, sizes = window_bits, Counter()
-    W = (scalar_bits + c - 1) // c
-    for i, s in enumerate(scalars):
-        if inf is not None and inf[i]:
-            continue
-        for w in range(W):
-            d = (s >> (w * c)) & ((1 << c) - 1)
-            if d and w == W - 1:
-                raise ValueError("scalar %d has a digit in the top window" % i)
-            if d:
-                sizes[(w, d)] += 1
-    return sizes
-
-
-def expected_lists(sizes, piece_len):
-    """the list counters a forced piece length leaves for buckets of these sizes: a bucket of sz > piece_len entries is cut into
-    m = ceil(sz / piece_len) pieces, each with a partial sum; m = 2: the two-piece list, 3 .. 7: the mid list, 8 or more: the long list with one
-    item per segment of 1024 pieces.  `pieces` counts every piece, those of whole buckets too."""
-    out = dict(long=0, mid=0, pieces=0, partials=0, mid2=0)
-    for sz in sizes:
-        m = 1 if sz <= piece_len else (sz + piece_len - 1) // piece_len
-        out["pieces"] += m
-        if m == 1:
-            continue
-        out["partials"] += m
-        if m == 2:
-            out["mid2"] += 1
-        elif m < LONG_SPAN:
-            out["mid"] += 1
-        else:
-            out["long"] += (m + LONG_SEG - 1) // LONG_SEG
-    return out
