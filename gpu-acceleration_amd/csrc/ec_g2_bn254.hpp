@@ -88,7 +88,7 @@ FP_HD xyzz2 xyzz2_add(const xyzz2& a, const xyzz2& b) {
     const fp2 ppp = fp2_mul<6>(pp, pp_);          // 1.6 * 10.4k + 1 < 1.1
     const fp2 qv = fp2_mul<3>(pp, u1);            // 1.6 * 4.4k + 1 < 1.05
     const fp2 x3 = fp2_sub<5>(fp2_sqr<6>(r), fp2_add(ppp, fp2_dbl(qv)));  // r^2 < 9 * 10k + 1 < 1.6, ppp + 2 qv < 3.2;  x3 < 6.6
-    const fp2 y3 = fp2_sub<3>(fp2_mul<10>(r, fp2_sub<8>(qv, x3)),         // qv - x3 < 9.1;  r * () < 4.5 * 19.2k + 1 < 1.6
+    const fp2 y3 = fp2_sub<3>(fp2_mul<10>(r, fp2_sub<8>(qv, x3)),         // x3 >= 1.8 (5p - 3.2p): qv - x3 < 1.05 + 8 - 1.8 < 7.3 (< 9: fp2_mul<10>);  r * () < 4.5 * 17.3k + 1 < 1.5
                               fp2_mul<3>(ppp, s1));                       // 1.1 * 4k + 1 < 1.03;  y3 < 4.6
     const fp2 zzz3 = fp2_mul<3>(fp2_mul<6>(a.zzz, b.zzz), ppp);          // < 1.3, then 1.3 * 3.2k + 1 < 1.03
     return xyzz2{x3, y3, zz3, zzz3};

@@ -244,6 +244,60 @@ int32_t msm_test_fr_raw_op(msm_ctx* c, uint32_t op, const uint32_t* a, const uin
     HIPCHK(c, hipMemcpy(out, dout, n * 36, hipMemcpyDeviceToHost));
     return MSM_OK;
 }
+// Fq and Fq2 on raw limb records (msmk::k_test_fq_raw / k_test_fq2_raw): checks, alloc / copy / launch / sync as msm_test_fr_raw_op.  in_words,
+// out_words: the words of an element; limbs_from: the first word of an element that must be a 29-bit limb (in_words: none)
+static int32_t run_fq_raw(msm_ctx* c, bool fq2, uint32_t op, const uint32_t* in, uint32_t* out, size_t n, size_t in_words, size_t out_words,
+                          size_t limbs_from) {
+    if (n == 0) return MSM_ERR_EMPTY;
+    if (n > 0x7FFFFFFFull / 45) return fail(c, MSM_ERR_BAD_ARG, "n too large");
+    // a limb of 2^29 or more could overflow a column accumulator of the multiplication: a malformed test is refused, not run
+    for (size_t i = 0; i < n * in_words; i++)
+        if (i % in_words >= limbs_from && in[i] > bn254::FP_MASK)
+            return fail(c, MSM_ERR_BAD_ARG, "in: word %zu of element %zu is not a 29-bit limb", i % in_words, i / in_words);
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    DevTmp tin, tout;  // freed on every exit path
+    HIPCHK(c, hipMalloc(&tin.p, n * in_words * 4));
+    HIPCHK(c, hipMalloc(&tout.p, n * out_words * 4));
+    HIPCHK(c, hipMemcpy(tin.p, in, n * in_words * 4, hipMemcpyHostToDevice));
+    const uint32_t* din = (const uint32_t*)tin.p;
+    uint32_t* dout = (uint32_t*)tout.p;
+#define MSM_FQ_RAW(KIND, K) \
+    case (KIND) | ((uint32_t)(K) << 8): msmk::k_test_fq_raw<KIND, K><<<grid1(n, 64), 64, 0, c->stream>>>(din, dout, (uint32_t)n); break;
+#define MSM_FQ2_RAW(KIND, K) \
+    case (KIND) | ((uint32_t)(K) << 8): msmk::k_test_fq2_raw<KIND, K><<<grid1(n, 64), 64, 0, c->stream>>>(din, dout, (uint32_t)n); break;
+    if (fq2) {
+        switch (op) { MSM_FQ2_RAW_OPS(MSM_FQ2_RAW) }
+    } else {
+        switch (op) { MSM_FQ_RAW_OPS(MSM_FQ_RAW) }
+    }
+#undef MSM_FQ_RAW
+#undef MSM_FQ2_RAW
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(out, dout, n * out_words * 4, hipMemcpyDeviceToHost));
+    return MSM_OK;
+}
+int32_t msm_test_fq_raw_op(msm_ctx* c, uint32_t op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!c || !in || !out) return MSM_ERR_BAD_ARG;
+    bool known = false;
+#define MSM_FQ_RAW(KIND, K) known = known || op == ((KIND) | ((uint32_t)(K) << 8));
+    MSM_FQ_RAW_OPS(MSM_FQ_RAW)
+#undef MSM_FQ_RAW
+    if (!known) return fail(c, MSM_ERR_BAD_ARG, "unknown raw Fq op %u (kind %u, K %u)", op, op & 0xFFu, op >> 8);
+    const uint32_t kind = op & 0xFFu;
+    const size_t in_words = (size_t)fqraw::fq_arity(kind) * 9;
+    return run_fq_raw(c, false, op, in, out, n, in_words, 9, fqraw::fq_any_limbs(kind) ? in_words : 0);
+}
+int32_t msm_test_fq2_raw_op(msm_ctx* c, uint32_t op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!c || !in || !out) return MSM_ERR_BAD_ARG;
+    bool known = false;
+#define MSM_FQ2_RAW(KIND, K) known = known || op == ((KIND) | ((uint32_t)(K) << 8));
+    MSM_FQ2_RAW_OPS(MSM_FQ2_RAW)
+#undef MSM_FQ2_RAW
+    if (!known) return fail(c, MSM_ERR_BAD_ARG, "unknown raw Fq2 op %u (kind %u, K %u)", op, op & 0xFFu, op >> 8);
+    return run_fq_raw(c, true, op, in, out, n, fqraw::fq2_words(op & 0xFFu), 18, 0);
+}
 int32_t msm_calibrate(msm_ctx* c, double* mad_per_s, double* fp_mul_per_s) {
     if (!c) return MSM_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->mu);

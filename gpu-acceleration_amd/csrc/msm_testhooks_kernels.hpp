@@ -7,6 +7,7 @@
 #include "msm_kernels.hpp"
 #include "msm_kernels_g2.hpp"
 #include "fr_bn254.hpp"
+#include "msm_testhooks_fq_raw.hpp"  // fqraw::fq_eval / fq2_eval, MSM_FQ_RAW_OPS
 #include "../../include/msm_hip_testhooks.h"  // MSM_OP_FR_RAW_*
 
 namespace msmk {
@@ -404,6 +405,23 @@ __global__ void __launch_bounds__(64) k_test_fr_raw(const uint32_t* __restrict__
 #pragma unroll
         for (int k = 0; k < 9; k++) op[k] = r.v[k];
     }
+}
+
+// the base field Fq of fp_bn254.hpp and Fq2 of fp2_bn254.hpp on RAW limb records (msm_test_fq_raw_op, msm_test_fq2_raw_op), the counterpart of
+// k_test_fr_raw for the field everything else stands on: one lane per element loads the words the caller wrote, calls the one function
+// (fqraw::fq_eval / fq2_eval of msm_testhooks_fq_raw.hpp, which tools/fq_bounds_check.cpp runs on the host) and stores the limbs it got.  One
+// kernel per (kind, K).  IN_WORDS: the words of an element.
+template <uint32_t KIND, int K>
+__global__ void __launch_bounds__(64) k_test_fq_raw(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fqraw::fq_eval<KIND, K>(in + (size_t)i * (fqraw::fq_arity(KIND) * 9), out + (size_t)i * 9);
+}
+template <uint32_t KIND, int K>
+__global__ void __launch_bounds__(64) k_test_fq2_raw(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fqraw::fq2_eval<KIND, K>(in + (size_t)i * fqraw::fq2_words(KIND), out + (size_t)i * 18);
 }
 
 }  // namespace msmk

@@ -19,7 +19,7 @@ HOOK_SYMBOLS = [
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
     "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2", "msm_test_g2_op", "msm_test_g1_raw_op",
-    "msm_test_fr_raw_op",
+    "msm_test_fr_raw_op", "msm_test_fq_raw_op", "msm_test_fq2_raw_op",
 ]
 OP_G2_MADD, OP_G2_ADD, OP_G2_DBL = 0, 1, 2  # MSM_OP_G2_* of include/msm_hip_testhooks.h
 # MSM_OP_G1_RAW_* of include/msm_hip_testhooks.h
@@ -33,6 +33,42 @@ FR_RAW_OPS = ("MUL", "ADD", "SUB2", "SUB3", "SUB7", "SUB8", "NORMALIZE", "REDUCE
 (OP_FR_RAW_MUL, OP_FR_RAW_ADD, OP_FR_RAW_SUB2, OP_FR_RAW_SUB3, OP_FR_RAW_SUB7, OP_FR_RAW_SUB8, OP_FR_RAW_NORMALIZE, OP_FR_RAW_REDUCE_LT2R,
  OP_FR_RAW_CANONICAL, OP_FR_RAW_UNPACK, OP_FR_RAW_PACK, OP_FR_RAW_FROM_STD, OP_FR_RAW_TO_STD, OP_FR_RAW_POW_U32, OP_FR_RAW_INV) = range(15)
 FR_RAW_NEEDS_B = (OP_FR_RAW_MUL, OP_FR_RAW_ADD, OP_FR_RAW_SUB2, OP_FR_RAW_SUB3, OP_FR_RAW_SUB7, OP_FR_RAW_SUB8, OP_FR_RAW_POW_U32)
+# MSM_OP_FQ_RAW_* / MSM_OP_FQ2_RAW_* of include/msm_hip_testhooks.h: op = kind | K << 8
+FQ_RAW_KINDS = ("MUL", "SQR", "MUL_ADD", "ADD", "DBL", "SUB", "NEG", "SUB_B_2C", "NORMALIZE", "REDUCE_LT2P", "CANONICAL", "INV", "IS_ZERO_LT2P", "UNPACK",
+                "UNPACK_SHL5", "FROM_MONT256", "FROM_STD", "PACK", "TO_MONT256", "TO_STD", "MUL_NEG_RAW2", "NORMALIZE_NEG_RAW2", "SUB6_NEG_RAW4", "Y3")
+FQ_RAW_ARITY = {"MUL": 2, "ADD": 2, "SUB": 2, "MUL_NEG_RAW2": 2, "SUB6_NEG_RAW4": 2, "SUB_B_2C": 3, "MUL_ADD": 4, "Y3": 5}  # records; the rest 1
+FQ_RAW_K = {"SUB": (2, 3, 4, 5, 6, 7, 8), "NEG": (2, 3, 4, 6), "Y3": (3, 6)}  # the pad multiples instantiated; the other kinds take K = 0
+FQ2_RAW_KINDS = ("MUL", "SQR", "SUB", "NEG", "ADD", "DBL", "MUL_FP", "IS_ZERO_LT2P", "IS_ZERO_ANY", "NEG_RAW6_MUL_ONE", "NEG_RAW6_MUL_FP", "CONJ")
+FQ2_RAW_WORDS = {"MUL": 36, "SUB": 36, "ADD": 36, "MUL_FP": 27, "NEG_RAW6_MUL_FP": 27}  # words of an element; the rest 18
+FQ2_RAW_K = {"MUL": (3, 4, 6, 7, 9, 10, 13, 15, 16, 17), "SQR": (3, 5, 6, 12, 13, 15, 16, 17), "SUB": (2, 3, 4, 5, 6, 7, 8, 9, 12, 13), "NEG": (2, 8),
+             "CONJ": (9, 13)}
+
+
+def fq_raw_op(kind, k=0):
+    """the op word of msm_test_fq_raw_op: kind (a name of FQ_RAW_KINDS) | K << 8"""
+    return FQ_RAW_KINDS.index(kind) | k << 8
+
+
+def fq2_raw_op(kind, k=0):
+    return FQ2_RAW_KINDS.index(kind) | k << 8
+
+
+def _raw_words(op, kinds, ks, words_of):
+    """the words of an element of `op`, ValueError for a kind or a K that is not instantiated"""
+    kind, k = op & 0xFF, op >> 8
+    if not 0 <= kind < len(kinds) or k not in ks.get(kinds[kind], (0,)):
+        raise ValueError(f"unknown raw op {op} (kind {kind}, K {k})")
+    return words_of(kinds[kind])
+
+
+def _elements(operands, words):
+    """n x words: a row of another width (a record missing, or one too many) is refused instead of being reshaped into other elements"""
+    a = np.ascontiguousarray(operands, dtype=np.uint32)
+    if a.ndim != 2 or a.shape[1] != words:
+        raise ValueError(f"operands must be n x {words} words, got {a.shape}")
+    return a
+
+
 _lib = None
 
 
@@ -58,6 +94,8 @@ def load_hooks_library():
     L.msm_test_g2_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_g1_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
     L.msm_test_fr_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_size_t]
+    L.msm_test_fq_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, C.c_size_t]
+    L.msm_test_fq2_raw_op.argtypes = [vp, C.c_uint32, _u32p, _u32p, C.c_size_t]
     L.msm_test_decompose.argtypes = [vp, _u32p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int32)]
     L.msm_test_abandon_after_sort.argtypes = [vp, _u32p, C.c_size_t]
     L.msm_calibrate.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -174,6 +212,26 @@ class HooksContext(MsmContext):
                 raise ValueError(f"a holds {a.shape[0]} records, b {b.shape[0]}")
         out = np.zeros_like(a)
         self._check(self._lib.msm_test_fr_raw_op(self._h, op, _p32(a), _p32(b), _p32(out), a.shape[0]))
+        return out
+
+    def test_fq_raw_op(self, op, operands):
+        """the base field on raw limb records (msm_test_fq_raw_op): op = fq_raw_op(kind, K); operands n x (ARITY * 9) words, the records of an
+        element one after the other (9 x 29-bit limbs each, any representative fp_bn254.hpp allows for the operation; the 8 words of a 256-bit
+        pattern and an ignored ninth for UNPACK, UNPACK_SHL5, FROM_MONT256, FROM_STD) -> n x 9 words, exactly what the device stored (word 8 is 0
+        where the function writes 8 words: PACK, TO_MONT256, TO_STD)"""
+        words = _raw_words(op, FQ_RAW_KINDS, FQ_RAW_K, lambda kind: 9 * FQ_RAW_ARITY.get(kind, 1))
+        a = _elements(operands, words)  # the C hook reads n x words: a shorter row must not reach it
+        out = np.zeros((a.shape[0], 9), np.uint32)
+        self._check(self._lib.msm_test_fq_raw_op(self._h, op, _p32(a), _p32(out), a.shape[0]))
+        return out
+
+    def test_fq2_raw_op(self, op, operands):
+        """Fq2 on raw limb records (msm_test_fq2_raw_op): op = fq2_raw_op(kind, K); operands n x FQ2_RAW_WORDS words (records of 18 words c0 c1;
+        the Fq operand of MUL_FP / NEG_RAW6_MUL_FP is 9 words) -> n x 18 words, exactly what the device stored"""
+        words = _raw_words(op, FQ2_RAW_KINDS, FQ2_RAW_K, lambda kind: FQ2_RAW_WORDS.get(kind, 18))
+        a = _elements(operands, words)
+        out = np.zeros((a.shape[0], 18), np.uint32)
+        self._check(self._lib.msm_test_fq2_raw_op(self._h, op, _p32(a), _p32(out), a.shape[0]))
         return out
 
     def ntt_set_tile_log2(self, tile_log2):

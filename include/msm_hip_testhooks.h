@@ -92,6 +92,53 @@ int32_t msm_test_g2_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint3
 #define MSM_OP_FR_RAW_POW_U32 13u     /* fr_pow_u32(a, b[0]): a < 84r */
 #define MSM_OP_FR_RAW_INV 14u         /* fr_inv(a): a < 84r */
 int32_t msm_test_fr_raw_op(msm_ctx *ctx, uint32_t op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n);
+/* the base field Fq of csrc/fp_bn254.hpp and Fq2 of csrc/fp2_bn254.hpp on RAW limb records: n elements, one device lane each, one function per
+ * launch, no conversion and no reduction on the way in or out.  A record is 9 words for Fq (9 limbs of 29 bits, one u32 word per limb, least
+ * significant first; value = sum limb_i * 2^(29 i)) and 18 words (c0, c1) for Fq2; ANY representative the value discipline of the two headers
+ * allows for the operation.  `in` holds n elements of ARITY records one after the other, `out` n records.  op = kind | K << 8, K the pad multiple
+ * where the function is a template over one (0 elsewhere); the instantiated (kind, K) are those of csrc/ outside the hooks files, any other is
+ * MSM_ERR_BAD_ARG.  A limb >= 2^29 in an operand that must be normalised is MSM_ERR_BAD_ARG before anything runs (the operand of NORMALIZE and
+ * the 8-word inputs take any 32-bit words); the value bounds are the caller's to keep: the device asserts nothing.  Where a function reads or
+ * writes 8 words (a 256-bit pattern) word 8 is ignored on input and written as 0 on output.  RAW values (fp_sub_raw / fp_neg_raw) never cross
+ * this interface: each way the product consumes one is a composite kind on normalised operands. */
+#define MSM_OP_FQ_RAW_MUL 0u                /* fp_mul(a, b): needs a * b < (2^261 - p) * 2^261 */
+#define MSM_OP_FQ_RAW_SQR 1u                /* fp_sqr(a) */
+#define MSM_OP_FQ_RAW_MUL_ADD 2u            /* fp_mul_add(a, b, c, d): needs a * b + c * d < (2^261 - p) * 2^261 */
+#define MSM_OP_FQ_RAW_ADD 3u                /* fp_add(a, b): a + b < 2^261 */
+#define MSM_OP_FQ_RAW_DBL 4u                /* fp_dbl(a) */
+#define MSM_OP_FQ_RAW_SUB 5u                /* fp_sub<K>(a, b): a + K p - b, b < (K-1) p;  K = 2 .. 8 */
+#define MSM_OP_FQ_RAW_NEG 6u                /* fp_neg<K>(a): K p - a;  K = 2, 3, 4, 6 */
+#define MSM_OP_FQ_RAW_SUB_B_2C 7u           /* fp_sub_b_2c(a, b, c): a + 5p - b - 2c, b + 2c < 4p */
+#define MSM_OP_FQ_RAW_NORMALIZE 8u          /* fp_normalize(a): limbs + carry < 2^32, value < 2^261 */
+#define MSM_OP_FQ_RAW_REDUCE_LT2P 9u        /* fp_reduce_lt2p(a): a < 2p */
+#define MSM_OP_FQ_RAW_CANONICAL 10u         /* fp_canonical(a) */
+#define MSM_OP_FQ_RAW_INV 11u               /* fp_inv(a): a < 2p */
+#define MSM_OP_FQ_RAW_IS_ZERO_LT2P 12u      /* fp_is_zero_lt2p(a): 0 or 1 in word 0, the other words 0 */
+#define MSM_OP_FQ_RAW_UNPACK 13u            /* fp_unpack(a[0..7]) */
+#define MSM_OP_FQ_RAW_UNPACK_SHL5 14u       /* fp_unpack_shl5(a[0..7]) */
+#define MSM_OP_FQ_RAW_FROM_MONT256 15u      /* fp_from_mont256(a[0..7]) */
+#define MSM_OP_FQ_RAW_FROM_STD 16u          /* fp_from_std(a[0..7]) */
+#define MSM_OP_FQ_RAW_PACK 17u              /* fp_pack(out[0..7], a): a < 2^256 */
+#define MSM_OP_FQ_RAW_TO_MONT256 18u        /* fp_to_mont256(out[0..7], a) */
+#define MSM_OP_FQ_RAW_TO_STD 19u            /* fp_to_std(out[0..7], a) */
+#define MSM_OP_FQ_RAW_MUL_NEG_RAW2 20u      /* fp_mul(fp_neg_raw<2>(a), b): the y of a negative digit into S2 (a < p) */
+#define MSM_OP_FQ_RAW_NORMALIZE_NEG_RAW2 21u /* fp_normalize(fp_neg_raw<2>(a)): xyzz_madd's identity branch */
+#define MSM_OP_FQ_RAW_SUB6_NEG_RAW4 22u     /* fp_sub<6>(fp_neg_raw<4>(a), b): the raw minuend of xyzz_madd_m32 */
+#define MSM_OP_FQ_RAW_Y3 23u                /* fp_mul_add(r, fp_sub_raw<8>(q, x3), fp_neg_raw<K>(y), ppp), records r q x3 y ppp;  K = 3, 6 */
+int32_t msm_test_fq_raw_op(msm_ctx *ctx, uint32_t op, const uint32_t *in, uint32_t *out, size_t n);
+#define MSM_OP_FQ2_RAW_MUL 0u               /* fp2_mul<K>(a, b): b.c1 < (K-1) p */
+#define MSM_OP_FQ2_RAW_SQR 1u               /* fp2_sqr<K>(a): a.c1 < (K-1) p */
+#define MSM_OP_FQ2_RAW_SUB 2u               /* fp2_sub<K>(a, b) */
+#define MSM_OP_FQ2_RAW_NEG 3u               /* fp2_neg<K>(a) */
+#define MSM_OP_FQ2_RAW_ADD 4u               /* fp2_add(a, b) */
+#define MSM_OP_FQ2_RAW_DBL 5u               /* fp2_dbl(a) */
+#define MSM_OP_FQ2_RAW_MUL_FP 6u            /* fp2_mul_fp(a, s): s one Fq record (9 words) */
+#define MSM_OP_FQ2_RAW_IS_ZERO_LT2P 7u      /* fp2_is_zero_lt2p(a): 0 or 1 in word 0, the other words 0 */
+#define MSM_OP_FQ2_RAW_IS_ZERO_ANY 8u       /* fp2_is_zero_any(a): likewise */
+#define MSM_OP_FQ2_RAW_NEG_RAW6_MUL_ONE 9u  /* fp_mul(fp_neg_raw_k<6>(a.ci), fp_one()) per component: g2_conj_small (a.ci < 5p) */
+#define MSM_OP_FQ2_RAW_NEG_RAW6_MUL_FP 10u  /* fp_mul(fp_neg_raw_k<6>(a.ci), s) per component, s one Fq record: fb2_inv_from_norm */
+#define MSM_OP_FQ2_RAW_CONJ 11u             /* {a.c0, fp_normalize(fp_neg_raw_k<K>(a.c1))}: the operand g2_conj_mul<K> builds;  K = 9, 13 */
+int32_t msm_test_fq2_raw_op(msm_ctx *ctx, uint32_t op, const uint32_t *in, uint32_t *out, size_t n);
 /* signed/unsigned digit decomposition of the planner's choice, digits[w*n + i] as int32 */
 int32_t msm_test_decompose(msm_ctx *ctx, const uint32_t *scalars, size_t n, uint32_t window_bits, int32_t *digits);
 
