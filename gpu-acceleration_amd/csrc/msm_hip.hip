@@ -50,6 +50,7 @@
 #include "msm_kernels_fixed_base.hpp"
 #include "msm_kernels_fixed_base_g2.hpp"
 #include "fr_vectors_bn254.hpp"
+#include "fr_scan_bn254.hpp"
 #include "msm_kernels_pointwise.hpp"
 #include "msm_kernels_g2_pointwise.hpp"
 #include "msm_kernels_g1_fft.hpp"
@@ -184,6 +185,7 @@ struct FixedBaseState;  // msm_fixed_base.inc
 struct FixedBaseG2State;  // msm_fixed_base.inc
 struct PointwiseState;  // msm_pointwise.inc
 struct GroupFftState;  // msm_g1_fft.inc
+struct FrScanState;  // msm_fr_scan.inc
 struct msm_ctx {
     std::mutex mu;
     Knobs knobs;
@@ -248,6 +250,7 @@ struct msm_ctx {
     FixedBaseG2State* fixed_base_g2 = nullptr;  // the same for G2, with the scratch array of its two-kernel chunks (msm_fixed_base.inc)
     PointwiseState* pointwise[2] = {};  // per group (PointSide<G>::RESULT) the staging arrays of the host-pointer element-wise multiplication, made by its first call (msm_pointwise.inc)
     GroupFftState* group_fft = nullptr;  // the twiddle tables of the G1 and G2 group transforms, one per size for both, and the staging arrays of their host-pointer forms (msm_g1_fft.inc)
+    FrScanState* fr_scan = nullptr;  // the block aggregates of the scalar-field scans and the event behind the latest of them, made by the first such call (msm_fr_scan.inc)
 };
 
 namespace {
@@ -257,6 +260,7 @@ void r1cs_release(msm_ctx* c);  // msm_r1cs.inc
 void fixed_base_release(msm_ctx* c);  // msm_fixed_base.inc (both groups)
 void pointwise_release(msm_ctx* c);  // msm_pointwise.inc (both groups)
 void group_fft_release(msm_ctx* c);  // msm_g1_fft.inc (both groups)
+void fr_scan_release(msm_ctx* c);  // msm_fr_scan.inc
 
 int32_t fail(msm_ctx* c, int32_t code, const char* fmt, ...) {
     char buf[512];
@@ -1607,6 +1611,7 @@ void msm_ctx_destroy(msm_ctx* c) {
         fixed_base_release(c);
         pointwise_release(c);
         group_fft_release(c);
+        fr_scan_release(c);
         DevBuf* bufs[] = {&c->bases,   &c->inf,       &c->scalars, &c->digits,  &c->ranks,  &c->sorted, &c->hist,
                           &c->offsets, &c->blocksums, &c->buckets, &c->rc,      &c->flags,  &c->pow2,
                           &c->sorttmp, &c->tilecounts, &c->ibases, &c->longlist, &c->longdone, &c->midlist, &c->ccounts, &c->cregion, &c->bigslot, &c->big,
@@ -2130,6 +2135,7 @@ int32_t msm_get_clock_stats(msm_ctx* c, double* sclk_ghz, double* cycles_per_add
 #include "msm_r1cs.inc"
 #include "msm_fixed_base.inc"
 #include "msm_fr_vectors.inc"
+#include "msm_fr_scan.inc"
 #include "msm_pointwise.inc"
 #include "msm_g1_fft.inc"
 

@@ -616,4 +616,16 @@ int32_t msm_test_ntt_set_tile_log2(msm_ctx* c, uint32_t tile_log2) {
     return MSM_OK;
 }
 
+int32_t msm_test_fr_scan_set_chain(msm_ctx* c, uint32_t chain) {
+    if (!c) return MSM_ERR_BAD_ARG;
+    if (chain != 0 && !fsck::fsc_chain_ok(chain))
+        return fail(c, MSM_ERR_BAD_ARG, "chain = %u: 0, %u or %u", chain, fsck::FSC_CHAIN_SMALL, fsck::FSC_CHAIN);
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    int32_t rc = fr_scan_state(c);
+    if (rc) return rc;
+    c->fr_scan->forced_chain = chain;
+    return MSM_OK;
+}
+
 }  // extern "C"

@@ -29,6 +29,7 @@ R1CS_COEF_STD, R1CS_COEF_MONT, R1CS_COEF_MONT2 = 0, 1, 2  # MSM_R1CS_COEF_*: a c
 R1CS_C_FROM_AB = 8  # MSM_R1CS_C_FROM_AB: the eval writes c[i] = a[i] * b[i] instead of (matrix 2) * w
 FB_OUT_STD = 8  # MSM_FB_OUT_STD: the fixed-base products come out in standard form (default: arkworks Montgomery words); NTT_IN_MONT is honoured too
 PM_BASES_STD = 16  # MSM_PM_BASES_STD: the bases of the element-wise multiplication are standard-form integers (default: arkworks Montgomery words)
+FR_SCAN_EXCLUSIVE = 32  # MSM_FR_SCAN_EXCLUSIVE: the running product starts at 1 and leaves the last element out (Z as PLONK stores it)
 G2_CHECK_CURVE, G2_CHECK_SUBGROUP = 1, 2  # MSM_G2_CHECK_*: coordinates < p and on the twist / [r]P = O (implies the curve check)
 OK, ERR_EMPTY, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_STATE, ERR_INVALID_DATA = 0, -1, -2, -3, -4, -5, -6, -7
 
@@ -51,6 +52,8 @@ ABI_SYMBOLS = [
     "msm_bn254_g2_fixed_base_plan", "msm_bn254_g2_fixed_base_mul_device", "msm_bn254_g2_fixed_base_mul",
     "msm_bn254_fr_vector_plan", "msm_bn254_fr_powers_device", "msm_bn254_fr_batch_inverse_device", "msm_bn254_fr_batch_inverse",
     "msm_bn254_fr_lagrange_device", "msm_bn254_fr_lincomb_device",
+    "msm_bn254_fr_scan_plan", "msm_bn254_fr_poly_eval_device", "msm_bn254_fr_poly_div_linear_device", "msm_bn254_fr_poly_div_linear",
+    "msm_bn254_fr_running_product_device",
     "msm_bn254_g1_pointwise_mul_plan", "msm_bn254_g1_pointwise_mul_device", "msm_bn254_g1_scale_device", "msm_bn254_g1_pointwise_mul",
     "msm_bn254_g1_fft_plan", "msm_bn254_g1_fft_device", "msm_bn254_g1_fft",
     "msm_bn254_g2_pointwise_mul_plan", "msm_bn254_g2_pointwise_mul_device", "msm_bn254_g2_scale_device", "msm_bn254_g2_pointwise_mul",
@@ -129,6 +132,15 @@ class FrVectorPlan(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class FrScanPlan(C.Structure):
+    """msm_fr_scan_plan_t: the chain of a lane, the elements of a workgroup, the launches and the scratch bytes of a scalar-field scan"""
+    _fields_ = [("chain", C.c_uint32), ("block_points", C.c_uint32), ("eval_launches", C.c_uint32), ("div_launches", C.c_uint32),
+                ("blocks", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PointwisePlan(C.Structure):
@@ -266,6 +278,11 @@ def bind_product_abi(L):
     L.msm_bn254_fr_batch_inverse.argtypes = [vp, _u32p, _u32p, C.c_size_t, C.c_uint32]
     L.msm_bn254_fr_lagrange_device.argtypes = [vp, _u32p, C.c_uint32, vp, C.c_uint32, vp]
     L.msm_bn254_fr_lincomb_device.argtypes = [vp, vp, _u32p, vp, _u32p, vp, _u32p, vp, C.c_size_t, C.c_uint32, vp]
+    L.msm_bn254_fr_scan_plan.argtypes = [C.c_size_t, C.POINTER(FrScanPlan)]
+    L.msm_bn254_fr_poly_eval_device.argtypes = [vp, vp, C.c_size_t, _u32p, vp, C.c_uint32, vp]
+    L.msm_bn254_fr_poly_div_linear_device.argtypes = [vp, vp, C.c_size_t, _u32p, vp, vp, C.c_uint32, vp]
+    L.msm_bn254_fr_poly_div_linear.argtypes = [vp, _u32p, C.c_size_t, _u32p, _u32p, _u32p, C.c_uint32]
+    L.msm_bn254_fr_running_product_device.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_uint32, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int:  # default
@@ -434,6 +451,17 @@ def fr_vector_plan():
     rc = lib.msm_bn254_fr_vector_plan(C.byref(p))
     if rc != OK:
         raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_fr_vector_plan failed ({rc})")
+    return p.as_dict()
+
+
+def fr_scan_plan(n):
+    """the chain of a lane, the elements of a workgroup, the kernel launches and the scratch bytes of a scalar-field scan over n elements, as a
+    dict of msm_fr_scan_plan_t (host only: no context, no GPU)"""
+    p = FrScanPlan()
+    lib = load_library()
+    rc = lib.msm_bn254_fr_scan_plan(n, C.byref(p))
+    if rc != OK:
+        raise MsmError(rc, (lib.msm_last_error(None) or b"").decode() or f"msm_bn254_fr_scan_plan failed ({rc})")
     return p.as_dict()
 
 
@@ -883,6 +911,40 @@ class MsmContext:
     @staticmethod
     def fr_vector_plan():
         return fr_vector_plan()
+
+    # -- BN254 scalar field: scans; the context keeps one array of block aggregates and the event behind the latest call ---
+    def fr_poly_eval_device(self, d_coeffs, n, z, d_value, flags=0, stream=None):
+        """d_value[0..8) = sum_i c[i] z^i on raw device pointers; z: an int or 8 standard-form words; flags NTT_IN_MONT / NTT_OUT_MONT; enqueued
+        on `stream` (None: the context's)"""
+        self._check(self._lib.msm_bn254_fr_poly_eval_device(self._h, d_coeffs, n, _p32(_fr_words(z)), d_value, flags, stream))
+
+    def fr_poly_div_linear_device(self, d_coeffs, n, z, d_quot, d_rem=None, flags=0, stream=None):
+        """p = q (X - z) + p(z) on raw device pointers: n elements q (q[n - 1] = 0) at d_quot, which may be d_coeffs, and p(z) at d_rem (8
+        words; None: not written); flags NTT_IN_MONT / NTT_OUT_MONT"""
+        self._check(self._lib.msm_bn254_fr_poly_div_linear_device(self._h, d_coeffs, n, _p32(_fr_words(z)), d_quot, d_rem, flags, stream))
+
+    def fr_poly_div_linear(self, coeffs, z, flags=0, out=None):
+        """host arrays: n x 8 words -> (the n x 8 words of the quotient, the 8 words of p(z)); the quotient is a new array or `out` (a contiguous
+        uint32 array, which may be `coeffs` itself)"""
+        a = _words(coeffs, 8)
+        if out is None:
+            out = np.zeros_like(a)
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.flags.c_contiguous and out.size == a.size):
+                raise MsmError(ERR_BAD_ARG, "out must be a contiguous uint32 array of the input's size")
+            out = out.reshape(-1, 8)
+        rem = np.zeros(8, np.uint32)
+        self._check(self._lib.msm_bn254_fr_poly_div_linear(self._h, _p32(a), a.shape[0], _p32(_fr_words(z)), _p32(out), _p32(rem), flags))
+        return out, rem
+
+    def fr_running_product_device(self, d_in, d_out, n, d_total=None, flags=0, stream=None):
+        """out[i] = in[0] .. in[i] on raw device pointers (with FR_SCAN_EXCLUSIVE: out[0] = 1, out[i] = in[0] .. in[i - 1]); the product of all
+        n at d_total (8 words; None: not written); d_out may be d_in; flags NTT_IN_MONT / NTT_OUT_MONT / FR_SCAN_EXCLUSIVE"""
+        self._check(self._lib.msm_bn254_fr_running_product_device(self._h, d_in, d_out, n, d_total, flags, stream))
+
+    @staticmethod
+    def fr_scan_plan(n):
+        return fr_scan_plan(n)
 
     # -- the host-array forms of the fixed-base and the element-wise calls; words: 16 per G1 point, 32 per G2 point; fn: the library's function ---
     def _fixed_base_host(self, words, fn, base, scalars, form, window_bits, flags):

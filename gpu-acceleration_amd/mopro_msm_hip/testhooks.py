@@ -19,7 +19,7 @@ HOOK_SYMBOLS = [
     "msm_test_decompose", "msm_calibrate", "msm_test_stage_dump", "msm_test_abandon_after_sort",
     "msm_probe_wide_level", "msm_probe_launch_chain", "msm_probe_empty_launch", "msm_test_get_list_counts", "msm_probe_reduce_bits",
     "msm_test_g2_sqrt", "msm_test_ntt_set_tile_log2", "msm_test_g2_op", "msm_test_g1_raw_op",
-    "msm_test_fr_raw_op", "msm_test_fq_raw_op", "msm_test_fq2_raw_op",
+    "msm_test_fr_raw_op", "msm_test_fq_raw_op", "msm_test_fq2_raw_op", "msm_test_fr_scan_set_chain",
 ]
 OP_G2_MADD, OP_G2_ADD, OP_G2_DBL = 0, 1, 2  # MSM_OP_G2_* of include/msm_hip_testhooks.h
 # MSM_OP_G1_RAW_* of include/msm_hip_testhooks.h
@@ -104,6 +104,7 @@ def load_hooks_library():
     L.msm_probe_empty_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     L.msm_test_get_list_counts.argtypes = [vp, _u32p]
     L.msm_test_ntt_set_tile_log2.argtypes = [vp, C.c_uint32]
+    L.msm_test_fr_scan_set_chain.argtypes = [vp, C.c_uint32]
     L.msm_probe_reduce_bits.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     L.msm_test_stage_dump.argtypes = [vp, _u32p, C.c_uint32, _u8p, _u32p, C.c_size_t, _u32p, _u32p, _u32p, _u32p, _u32p,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _u32p]
@@ -237,6 +238,10 @@ class HooksContext(MsmContext):
     def ntt_set_tile_log2(self, tile_log2):
         """the LDS tile (log2 elements) of the transforms that follow on this context: 4 or 10; 0 = the plan's own"""
         self._check(self._lib.msm_test_ntt_set_tile_log2(self._h, tile_log2))
+
+    def fr_scan_set_chain(self, chain):
+        """the elements per lane of the scalar-field scans that follow on this context: 1 or 8; 0 = the plan's own"""
+        self._check(self._lib.msm_test_fr_scan_set_chain(self._h, chain))
 
     def abandon_after_sort(self, scalars):
         """decomposition + sort + piece plan of an MSM on `scalars`, then the failure a copy / event wait in front of the accumulation would be:

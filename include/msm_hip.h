@@ -740,6 +740,48 @@ int32_t msm_bn254_fr_lagrange_device(msm_ctx *ctx, const uint32_t *tau_std, uint
 int32_t msm_bn254_fr_lincomb_device(msm_ctx *ctx, const void *d_a, const uint32_t *ka_std, const void *d_b, const uint32_t *kb_std,
                                     const void *d_c, const uint32_t *kc_std, void *d_out, size_t n, uint32_t flags, void *hip_stream);
 
+/* ---- BN254 scalar field Fr: scans (ABI 7) -- calls whose output element depends on EVERYTHING after or before it: the
+ *      value of a polynomial at a point, its quotient by X - z (the proof of a KZG opening is the MSM of that quotient) and the running
+ *      product (the grand product Z of PLONK and halo2).  Conventions of the Fr-vector section above: elements are 8 little-endian words; any
+ *      256-bit input pattern is read modulo r; outputs are canonical (< r), so results are bit-exact; MSM_NTT_IN_MONT / MSM_NTT_OUT_MONT name
+ *      the form of the DEVICE arrays; z is a HOST pointer to 8 standard-form words, read modulo r; device arrays are 16-byte aligned.
+ *      Stream-ordered on hip_stream (NULL = the context's stream): a call returns when enqueued, and a single value (d_value, d_rem, d_total)
+ *      is written to DEVICE memory.  A call is two (evaluation) or three kernel launches with a scratch array between them.
+ *      UNLIKE the Fr vectors, this family keeps ONE array on the context: the aggregates of the workgroups (36 bytes per block_points elements,
+ *      grown on demand, freed by msm_ctx_destroy).  The ordering rule is the transforms': every call leaves an event behind, and a call on
+ *      ANOTHER stream than the previous one waits for it first.  The caller orders calls that share a data array.
+ *      Errors: a NULL or misaligned pointer, an unknown flag bit, n > 2^36: MSM_ERR_BAD_ARG; n == 0: MSM_ERR_EMPTY; allocation failure:
+ *      MSM_ERR_OOM.  A failed call has written nothing and the context stays usable. ---- */
+#define MSM_FR_SCAN_EXCLUSIVE 32u /* msm_bn254_fr_running_product_device: out[0] = 1, out[i] = in[0] * .. * in[i - 1] (Z as PLONK stores it) */
+typedef struct {
+    uint32_t chain;          /* consecutive elements one lane folds */
+    uint32_t block_points;   /* consecutive elements one workgroup covers: 256 * chain */
+    uint32_t eval_launches;  /* kernel launches of msm_bn254_fr_poly_eval_device */
+    uint32_t div_launches;   /* ... of msm_bn254_fr_poly_div_linear_device and of msm_bn254_fr_running_product_device */
+    uint64_t blocks;         /* workgroups of the first and the last launch for n: ceil(n / block_points); the launch between is ONE workgroup
+                              * that walks them in ceil(blocks / 256) rounds */
+    uint64_t scratch_bytes;  /* kept on the context for n: 36 * blocks */
+} msm_fr_scan_plan_t;
+/* host only, no context (32 bytes: the library and tests/test_fr_scan_cpu.py assert the size).  n == 0: MSM_ERR_EMPTY; n > 2^36 or out NULL: MSM_ERR_BAD_ARG */
+int32_t msm_bn254_fr_scan_plan(size_t n, msm_fr_scan_plan_t *out);
+/* d_value[0..8) = sum_{i < n} c[i] * z^i. */
+int32_t msm_bn254_fr_poly_eval_device(msm_ctx *ctx, const void *d_coeffs, size_t n, const uint32_t *z_std, void *d_value, uint32_t flags,
+                                      void *hip_stream);
+/* p(X) = q(X) * (X - z) + p(z):  d_quot receives n elements, q[j] = sum_{i > j} c[i] * z^(i - j - 1) for j < n - 1 and q[n - 1] = 0 (the array
+ * keeps the length of the base set its MSM runs against); d_rem (8 words, may be NULL) receives p(z).  d_quot may be d_coeffs.  n == 1:
+ * q[0] = 0 and the remainder is c[0].  z = 0 is an ordinary input (the quotient is the shift): nothing is inverted. */
+int32_t msm_bn254_fr_poly_div_linear_device(msm_ctx *ctx, const void *d_coeffs, size_t n, const uint32_t *z_std, void *d_quot, void *d_rem,
+                                            uint32_t flags, void *hip_stream);
+/* host pointers, blocking; quot == coeffs allowed, rem may be NULL; stages through a device allocation of n * 32 + 32 bytes that is freed
+ * before the call returns.  Pageable memory is pinned in place like every host-pointer call. */
+int32_t msm_bn254_fr_poly_div_linear(msm_ctx *ctx, const uint32_t *coeffs, size_t n, const uint32_t *z_std, uint32_t *quot, uint32_t *rem,
+                                     uint32_t flags);
+/* out[i] = in[0] * .. * in[i]; with MSM_FR_SCAN_EXCLUSIVE out[0] = 1 and out[i] = in[0] * .. * in[i - 1].  d_total (8 words, may be NULL)
+ * receives the product of all n elements in either mode.  d_out may be d_in.  An element = 0 (mod r) zeroes everything after it.
+ * flags: MSM_NTT_IN_MONT, MSM_NTT_OUT_MONT, MSM_FR_SCAN_EXCLUSIVE. */
+int32_t msm_bn254_fr_running_product_device(msm_ctx *ctx, const void *d_in, void *d_out, size_t n, void *d_total, uint32_t flags,
+                                            void *hip_stream);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 /* the plan of a call on n points under (window_bits, flags); with MSM_FLAG_WINDOW_TABLE in flags: the plan of a RESIDENT call on a
  * set of n bases uploaded under those flags (window width, table factor, table memory) */

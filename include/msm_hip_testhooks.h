@@ -205,6 +205,10 @@ int32_t msm_test_get_list_counts(msm_ctx *ctx, uint32_t out[5]);
 /* the tile size (log2 of the elements a workgroup holds in LDS) of the transforms that follow on this context: 4 or 10, the two sizes the
  * kernels are instantiated for; 0 = back to the plan of msm_bn254_fr_ntt_plan.  With 4, 2^12 elements are a three-pass transform. */
 int32_t msm_test_ntt_set_tile_log2(msm_ctx *ctx, uint32_t tile_log2);
+/* the chain (elements per lane) of the scalar-field scans that follow on this context: 1 or 8, the two lengths the kernels are instantiated
+ * for; 0 = back to the plan of msm_bn254_fr_scan_plan.  With 1 a workgroup covers 256 elements, and the launch that walks the workgroups'
+ * aggregates needs a second round from 2^16 + 1 elements on. */
+int32_t msm_test_fr_scan_set_chain(msm_ctx *ctx, uint32_t chain);
 
 #ifdef __cplusplus
 }

@@ -261,6 +261,44 @@ extern "C" {
     ) -> i32;
 }
 
+/// MSM_FR_SCAN_EXCLUSIVE: the running product starts at 1 and leaves the last element out
+pub const MSM_FR_SCAN_EXCLUSIVE: u32 = 32;
+
+/// msm_fr_scan_plan_t: the chain of a lane, the elements of a workgroup, the launches and the scratch bytes of a scalar-field scan
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct MsmFrScanPlan {
+    pub chain: u32,
+    pub block_points: u32,
+    pub eval_launches: u32,
+    pub div_launches: u32,
+    pub blocks: u64,
+    pub scratch_bytes: u64,
+}
+
+// Scans over the scalar field made in HBM (include/msm_hip.h): the value of a polynomial at z, its quotient by X - z (the
+// proof of a KZG opening is the MSM of that quotient) and the running product.  z is a host pointer to 8 standard-form words; the single
+// values are written to device memory.  The context keeps one scratch array and orders calls on different streams.  Declarations only.
+#[allow(dead_code)]
+extern "C" {
+    pub fn msm_bn254_fr_scan_plan(n: usize, out: *mut MsmFrScanPlan) -> i32;
+    pub fn msm_bn254_fr_poly_eval_device(
+        ctx: *mut MsmCtx, d_coeffs: *const core::ffi::c_void, n: usize, z_std: *const u32, d_value: *mut core::ffi::c_void, flags: u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_poly_div_linear_device(
+        ctx: *mut MsmCtx, d_coeffs: *const core::ffi::c_void, n: usize, z_std: *const u32, d_quot: *mut core::ffi::c_void,
+        d_rem: *mut core::ffi::c_void, flags: u32, hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+    pub fn msm_bn254_fr_poly_div_linear(
+        ctx: *mut MsmCtx, coeffs: *const u32, n: usize, z_std: *const u32, quot: *mut u32, rem: *mut u32, flags: u32,
+    ) -> i32;
+    pub fn msm_bn254_fr_running_product_device(
+        ctx: *mut MsmCtx, d_in: *const core::ffi::c_void, d_out: *mut core::ffi::c_void, n: usize, d_total: *mut core::ffi::c_void, flags: u32,
+        hip_stream: *mut core::ffi::c_void,
+    ) -> i32;
+}
+
 /// msm_pointwise_plan_t: the inversion group, the ladder's positions and the points a lane keeps of an element-wise multiplication
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
